@@ -10,7 +10,9 @@ Inputs are resident in HBM before the timed region.  N>1: one process per GPU (t
 shard across ranks with no data-path collective (weak scaling); the timed region is bracketed by
 barrier + synchronize and the max over ranks is reported.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps, writes the last timed step's features when
+--dump-outputs DIR is given and prints the line: `value` (clips/s) and `ms_per_step` are its headline.  --full adds the extra objects
+below (each can still be switched off with its --no-* flag under --full):
   roofline      dominant kernel (gemm16*: fp16 MFMA GEMM; "_w2" = 2-pass weights-split variant) — algorithmic 2*M*N*K FLOPs of its launches
                 divided by their HIP-event durations (measured in a second, instrumented pass over
                 the same steps), against the 2.5 PFLOP/s dense fp16 MFMA peak.
@@ -19,7 +21,9 @@ Prints ONE JSON line (rank 0).  Extra objects:
                 timing rides along as oracle_port.
   parity        max|x-ref|/max|ref| of the first two clips' features of the LAST timed step (the full-batch kernel selection)
                 against the CPU oracle, per modality; the run fails when one exceeds 1e-3.
-N > 1 without torchrun: bench.py re-executes itself under torch.distributed.run (one rank per GPU) and fails loudly when
+  sustained, large, ladder, e2e   the same step for >= --sustain-seconds, the large trio (BASELINE configs[4]), the headline step on
+                the other precision rungs, and files -> .npy through the drop-in drivers (see main()).
+N > 1 without torchrun: bench.py runs itself under torch.distributed.run in a child process (one rank per GPU) and fails loudly when
 the box has fewer than N GPUs.  Under N > 1 every step also issues the fusion minibatch exchange of BASELINE configs[3]
 (distributed.gather_fusion_batch: ONE fused RCCL all-gather of the [B, Da+Dt+Dv] feature rows) on a side stream; its
 duration is reported separately ("allgather") and it overlaps the next step's extraction.
@@ -78,6 +82,11 @@ def parse():
                                                            "(kernels of one sub-batch fill the partial last wave of workgroups of the other)")
     ap.add_argument("--split-mods", default="avt", help="modalities --split applies to (the others run their whole batch on one stream)")
     ap.add_argument("--force-dist", action="store_true", help="run the N > 1 code path with a one-rank RCCL group (self-test on a 1-GPU box)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the features of the last timed step as DIR/{audio,visual,text}.npy (float32; rank 0's clips; at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the headline figure: roofline pass, parity vs the CPU oracle, "
+                                                        "sustained line, large trio, precision ladder, e2e drivers, CPU baseline (the --no-* flags below "
+                                                        "switch single ones off)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the oracle comparison of the last step's first two clips")
     ap.add_argument("--no-roofline", action="store_true")
@@ -86,8 +95,11 @@ def parse():
     ap.add_argument("--no-ladder", action="store_true", help="skip the `ladder` sub-object (the same step under the precision rungs a load-time self-check can move an encoder to)")
     ap.add_argument("--sustain-seconds", type=float, default=20.0)
     ap.add_argument("--e2e-cold-child", default=None, help=argparse.SUPPRESS)   # internal: the fresh process e2e() spawns over its corpus directory
-    ap.add_argument("--e2e", type=int, default=1024, help="N > 0: also run N clips files -> .npy through the drop-in drivers (extra key `e2e`, headline line on one GPU only); 0 skips it")
-    return ap.parse_args()
+    ap.add_argument("--e2e", type=int, default=1024, help="with --full, N > 0: also run N clips files -> .npy through the drop-in drivers (extra key `e2e`, headline line on one GPU only); 0 skips it")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def _cpu_model():
@@ -245,7 +257,9 @@ def pmc_mfma_busy(kernel, root=ROOT):
 
 
 def respawn_under_torchrun(args):
-    """`python bench.py --gpus N` (N > 1) outside torchrun: one rank per GPU via torch.distributed.run, same flags."""
+    """`python bench.py --gpus N` (N > 1) outside torchrun: one rank per GPU via torch.distributed.run, same flags, in a child process
+    (this one has touched the HIP runtime to count the GPUs, so it is not replaced by exec); exits with the child's status."""
+    import subprocess
     n = torch.cuda.device_count()
     if n < args.gpus:
         sys.exit(f"bench.py: --gpus {args.gpus} but this box has {n} visible GPU(s); refusing to run fewer ranks than asked "
@@ -256,7 +270,7 @@ def respawn_under_torchrun(args):
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execv(sys.executable, cmd)
+    sys.exit(subprocess.call(cmd))
 
 
 def oracle_features(kind, size, x):
@@ -430,7 +444,7 @@ def measure(args, config, steps, warmup, dev, dist, rank, world, sustain_s=0.0, 
     feats = {m: torch.cat(out[m], 0) for m in out}
     for o in feats.values():
         assert torch.isfinite(o).all(), "non-finite features"
-    res = {"value": B * world * steps / dt, "ms_per_step": dt / steps * 1e3, "dt": dt, "sub_batches": {m: Sm[m] for m in sorted(mods)}}
+    res = {"value": B * world * steps / dt, "ms_per_step": dt / steps * 1e3, "dt": dt, "sub_batches": {m: Sm[m] for m in sorted(mods)}, "feats": feats}
     if comm is not None:
         assert full[0].shape == (B * world, feats["a"].shape[1]) and torch.equal(full[0][rank * B:(rank + 1) * B], feats["a"]), \
             "fusion minibatch exchange: this rank's rows did not come back in rank order"
@@ -755,6 +769,21 @@ def e2e(args, dev):
         shutil.rmtree(root, ignore_errors=True)
 
 
+DUMP_NAMES = {"a": "audio", "v": "visual", "t": "text"}
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(feats, out_dir):
+    """The last timed step's features, as a caller of the step receives them, to out_dir/{audio,visual,text}.npy (float32 [clips, D]).
+    Above DUMP_MAX_BYTES in all, every k-th clip (the same clips in each file) is kept: a fixed sample, the same from run to run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {DUMP_NAMES[m]: x.float().cpu().numpy() for m, x in sorted(feats.items())}
+    stride = -(-sum(a.nbytes for a in arrs.values()) // DUMP_MAX_BYTES)
+    for name, a in arrs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a[::stride]))
+
+
 def main():
     args = parse()
     if args.e2e_cold_child:
@@ -796,14 +825,17 @@ def main():
     B = args.batch
     cfgset = CONFIGS[args.config]
     headline = args.config == "base" and mods == set("avt")
-    r = measure(args, args.config, args.steps, args.warmup, dev, dist, rank, world, sustain_s=0.0 if args.no_sustained else args.sustain_seconds,
-                want_roofline=not args.no_roofline, want_parity=not args.no_parity)
+    full = args.full
+    r = measure(args, args.config, args.steps, args.warmup, dev, dist, rank, world, sustain_s=args.sustain_seconds if full and not args.no_sustained else 0.0,
+                want_roofline=full and not args.no_roofline, want_parity=full and not args.no_parity)
     parity = r.get("parity")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(r["feats"], args.dump_outputs)
 
     # BASELINE.json configs[4] (the large trio) rides along in the headline line as a sub-object: its own short timed region, roofline
     # fraction and parity.  Served with f16 MFMA operands (same MFMA rate as bf16 on gfx950, three more mantissa bits: DESIGN.md §4).
     large = None
-    if headline and not args.no_large:
+    if full and headline and not args.no_large:
         try:
             lr = measure(args, "large", max(2, min(args.steps, 4)), 1, dev, dist, rank, world, want_roofline=not args.no_roofline, want_parity=not args.no_parity)
             large = {"workload": CONFIGS["large"]["workload"], "value": round(lr["value"], 2), "unit": "clips/s", "ms_per_step": round(lr["ms_per_step"], 3),
@@ -824,7 +856,7 @@ def main():
     # moves an encoder whose checkpoint does not hold 1e-3 under the one-plane default up the ladder (encoders._self_check), so the deployed
     # rate of a real checkpoint lies between `value` (no encoder escalated: what random-init weights give) and the `accurate` figure here.
     ladder = None
-    if headline and not args.no_ladder and world == 1 and args.precision == "mean":
+    if full and headline and not args.no_ladder and world == 1 and args.precision == "mean":
         import copy
         ladder = {"what": "the same step with EVERY encoder on that rung (a self-check moves encoders individually: mean_conv3 only exists for the audio encoder)",
                   "steps": 3, "mean": round(r["value"], 2)}
@@ -862,7 +894,7 @@ def main():
             res["large"] = large
         if ladder is not None:
             res["ladder"] = ladder
-        if args.e2e > 0 and world == 1 and headline:
+        if full and args.e2e > 0 and world == 1 and headline:
             try:
                 res["e2e"] = e2e(args, dev)
                 res["e2e"]["frac_of_three_stream_kernel_only"] = round(res["e2e"]["clips_per_s"] / r["value"], 3)
@@ -870,7 +902,7 @@ def main():
                     res["e2e"]["trimodal_pipeline"]["frac_of_three_stream_kernel_only"] = round(res["e2e"]["trimodal_pipeline"]["clips_per_s"] / r["value"], 3)
             except Exception as e:
                 res["e2e"] = {"error": repr(e)}
-        if not args.no_cpu_baseline and world == 1:
+        if full and not args.no_cpu_baseline and world == 1:
             try:
                 if args.config == "base":
                     res["cpu_baseline"] = cpu_baseline()

@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 6: the headline step and the per-modality lines (kernel-only), + rocprofv3 kernel stats of the headline / audio-b32 steps.  Usage: bash scripts/gpu_r6_bench.sh <tag> [noprof]
 tag=${1:-r6b}; cd "${GRAFT_REPO_ROOT:-.}"; O=gpurun_out/$tag; mkdir -p "$O"; export TMPDIR=/tmp; R=$PWD
-Q="--no-cpu-baseline --no-sustained --no-large --no-ladder --e2e 0"
+Q="--full --no-cpu-baseline --no-sustained --no-large --no-ladder --e2e 0"
 timeout 300 python bench.py --steps 20 --warmup 5 $Q > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
 timeout 200 python bench.py --steps 20 --warmup 5 --modalities v $Q > $O/bench_visual_b64.json 2>> $O/bench.err; echo "visual rc=$?"
 timeout 200 python bench.py --steps 20 --warmup 5 --modalities a --batch 32 $Q > $O/bench_audio_b32.json 2>> $O/bench.err; echo "audio32 rc=$?"

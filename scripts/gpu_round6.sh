@@ -11,13 +11,13 @@ R=$PWD
 timeout 60 scripts/probes/abi_selftest.bin > "$O/abi_selftest.jsonl" 2>&1; echo "abi rc=$?"
 timeout 1500 python -m pytest tests -m gpu -q -s --no-header -p no:cacheprovider > "$O/suite.log" 2>&1; echo "suite rc=$?"; grep -E "passed|failed|^FAILED|^ERROR" "$O/suite.log" | tail -8
 grep -E "(utt|frames?)( diff)?=|self-check|escalated|by name" "$O/suite.log" | grep -v "print(" > "$O/parity_lines.txt"
-timeout 900 python bench.py --steps 20 --warmup 5 > "$O/bench.json" 2> "$O/bench.err"; echo "bench rc=$?"
-timeout 200 python bench.py --steps 20 --warmup 5 --modalities a --batch 32 --no-cpu-baseline --no-sustained --no-ladder --e2e 0 > "$O/bench_audio_b32.json" 2>> "$O/bench.err"; echo "audio rc=$?"
-timeout 200 python bench.py --steps 20 --warmup 5 --modalities a --no-cpu-baseline --no-sustained --no-ladder --e2e 0 > "$O/bench_audio_b64.json" 2>> "$O/bench.err"; echo "audio64 rc=$?"
-timeout 200 python bench.py --steps 20 --warmup 5 --modalities v --no-cpu-baseline --no-sustained --no-ladder --e2e 0 > "$O/bench_visual_b64.json" 2>> "$O/bench.err"; echo "visual rc=$?"
-timeout 200 python bench.py --steps 20 --warmup 5 --modalities t --no-cpu-baseline --no-sustained --no-ladder --e2e 0 > "$O/bench_text_b64.json" 2>> "$O/bench.err"; echo "text rc=$?"
+timeout 900 python bench.py --full --steps 20 --warmup 5 > "$O/bench.json" 2> "$O/bench.err"; echo "bench rc=$?"
+timeout 200 python bench.py --full --steps 20 --warmup 5 --modalities a --batch 32 --no-cpu-baseline --no-sustained --no-ladder --e2e 0 > "$O/bench_audio_b32.json" 2>> "$O/bench.err"; echo "audio rc=$?"
+timeout 200 python bench.py --full --steps 20 --warmup 5 --modalities a --no-cpu-baseline --no-sustained --no-ladder --e2e 0 > "$O/bench_audio_b64.json" 2>> "$O/bench.err"; echo "audio64 rc=$?"
+timeout 200 python bench.py --full --steps 20 --warmup 5 --modalities v --no-cpu-baseline --no-sustained --no-ladder --e2e 0 > "$O/bench_visual_b64.json" 2>> "$O/bench.err"; echo "visual rc=$?"
+timeout 200 python bench.py --full --steps 20 --warmup 5 --modalities t --no-cpu-baseline --no-sustained --no-ladder --e2e 0 > "$O/bench_text_b64.json" 2>> "$O/bench.err"; echo "text rc=$?"
 for prec in mx balanced; do   # the other one-plane presets on the same box (the ladder rungs ride in the default line: `ladder`)
-  timeout 300 python bench.py --steps 20 --warmup 5 --precision $prec --no-cpu-baseline --no-sustained --no-large --no-ladder --e2e 0 > "$O/bench_$prec.json" 2>> "$O/bench.err"; echo "$prec rc=$?"
+  timeout 300 python bench.py --full --steps 20 --warmup 5 --precision $prec --no-cpu-baseline --no-sustained --no-large --no-ladder --e2e 0 > "$O/bench_$prec.json" 2>> "$O/bench.err"; echo "$prec rc=$?"
 done
 prof() {  # name, bench flags...
   local name=$1; shift
@@ -43,7 +43,7 @@ MER_CHECK=1 MER_DECOMP=1 MER_STAGGER_AB=1 timeout 500 scripts/probes/gemm16_benc
 timeout 300 python scripts/load_time_ladder.py > "$O/load_time_ladder.json" 2>/dev/null; echo "load_time rc=$?"
 # the headline line once more, now that the PMC collections of THIS tree exist next to it (roofline.traffic / mfma_busy filled in)
 mkdir -p profiles_tmp && cp "$O/pmc_hbm_traffic.json" profiles/r06_pmc_hbm_traffic.json 2>/dev/null; cp "$O/pmc_mfma.json" profiles/r06_pmc_mfma.json 2>/dev/null; rmdir profiles_tmp
-timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-sustained --no-large --no-ladder --e2e 0 > "$O/bench_with_pmc.json" 2>> "$O/bench.err"; echo "bench+pmc rc=$?"
+timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-sustained --no-large --no-ladder --e2e 0 > "$O/bench_with_pmc.json" 2>> "$O/bench.err"; echo "bench+pmc rc=$?"
 python - "$O" <<'P'
 import json, sys
 O = sys.argv[1]

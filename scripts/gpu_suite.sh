@@ -21,7 +21,7 @@ if [[ $what == tests || $what == all ]]; then
   run smoke 300 python __graft_entry__.py smoke
 fi
 if [[ $what == bench || $what == all ]]; then
-  run bench 900 python bench.py --steps 5 --warmup 2
+  run bench 900 python bench.py --full --steps 5 --warmup 2
 fi
 if [[ $what == prof || $what == all ]]; then
   rm -rf gpurun_out/prof

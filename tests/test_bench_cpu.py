@@ -61,3 +61,32 @@ def test_stale_pmc_collection_is_refused(tmp_path):
     d.pop("_source_sha")
     json.dump(d, open(root / "profiles" / os.path.basename(pmc), "w"))
     assert b.pmc_traffic("gemm16p", 5e8, root=str(root))[0] is None
+
+
+def test_dump_outputs_writes_float32_features_within_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 [clips, D] file per modality, the same clips in each; above the cap a fixed every-k-th-clip sample."""
+    import numpy as np
+    import torch
+    b = _bench()
+    g = torch.Generator().manual_seed(0)
+    feats = {"a": torch.randn(64, 768, generator=g), "v": torch.randn(64, 512, generator=g).half(), "t": torch.randn(64, 768, generator=g)}
+    b.dump_outputs(feats, str(tmp_path / "all"))
+    for m, name in b.DUMP_NAMES.items():
+        x = np.load(tmp_path / "all" / f"{name}.npy")
+        assert x.dtype == np.float32 and np.array_equal(x, feats[m].float().numpy())
+    monkeypatch.setattr(b, "DUMP_MAX_BYTES", 100_000)
+    b.dump_outputs(feats, str(tmp_path / "cap"))
+    got = {name: np.load(tmp_path / "cap" / f"{name}.npy") for name in b.DUMP_NAMES.values()}
+    assert sum(x.nbytes for x in got.values()) <= 100_000
+    assert np.array_equal(got["audio"], feats["a"].numpy()[::6]) and got["visual"].shape == (11, 512)
+
+
+def test_plain_run_by_default_and_steps_validated(monkeypatch):
+    import pytest
+    b = _bench()
+    monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "7"])
+    a = b.parse()
+    assert a.steps == 7 and not a.full and a.dump_outputs is None
+    monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        b.parse()

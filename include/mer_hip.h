@@ -310,6 +310,44 @@ int mer_adam_step_dev(float* p, const float* g, float* m, float* v, long long n,
                       float weight_decay, int* step_dev, float clip_value, mer_stream_t stream);
 int mer_inc_i32(int* x, mer_stream_t stream);
 
+/* ---- grouped fusion training (csrc/fusion_group.hip): G independent Attention models (feat_type utt, emotion + valence
+ *      heads, MERBench/toolkit/models/attention.py:36-57) — e.g. the 5 folds of a CV run times N trials — trained in ONE
+ *      step whose launch count does not depend on G.  Parameters / gradients / Adam moments are [G, P] fp32, each row in
+ *      model.parameters() order: {audio, text, video}_encoder.linear_{1,2,3}.{weight, bias}, attention_mlp.linear_{1,2,3},
+ *      fc_att, fc_out_1, fc_out_2 (mer_fusion_group_param_count gives P).  Step s reads rows index[s, g, :count[s, g]]
+ *      of the device-resident split tables for model g (count 0: g idle, nothing of it is touched), s = *cursor (0 when
+ *      cursor is NULL), and writes loss [s, g], emotion logits [s, g, :, C1] and valence [s, g, :] to the out_* epoch buffers;
+ *      the step's last launch advances *cursor, so a captured step replays through an epoch's [n_steps, G, B] table.
+ *      Model g's results are bitwise those of a group holding g alone, and at dropout 0 those of the single-model kernels
+ *      (FusionGraphTrainer).  Dropout masks come from a counter-based hash of (seed[g], step[g], site, row, col),
+ *      documented in csrc/fusion_group.hip; train steps bump step[g] of every active model.  Eval steps (train = 0): forward
+ *      and losses only, no dropout, counters unchanged.  A step allocates nothing and never synchronises. */
+typedef struct {
+  int G, B, n_steps;                 /* models, rows per minibatch (<= 2048), steps in the index / count / out_* tables */
+  int Da, Dt, Dv, H, C1, C2;         /* audio / text / video input dims, hidden dim, emotion classes (<= 64), valence outputs (1) */
+  long long P;                       /* parameters per model */
+  float* params; float* grads; float* adam_m; float* adam_v;   /* [G, P] */
+  int* step;                         /* [G] optimiser steps taken (Adam bias correction uses step + 1) */
+  const float* lr; const float* weight_decay; const float* grad_clip; const float* dropout;   /* [G]; grad_clip <= 0: none */
+  const uint64_t* seed;              /* [G] dropout seeds (may be NULL: 0) */
+  float beta1, beta2, eps;
+  const float* feat_a; const float* feat_t; const float* feat_v;   /* split tables [n_rows, D*] */
+  const int* emo; const float* val;  /* [n_rows] class index, valence */
+  long long n_rows;
+  const int* index;                  /* [n_steps, G, B] table rows */
+  const int* count;                  /* [n_steps, G] rows used (<= B) */
+  int* cursor;                       /* current step, advanced by each step (may be NULL) */
+  float* out_loss; float* out_emo; float* out_val;   /* [n_steps, G], [n_steps, G, B, C1], [n_steps, G, B]; each may be NULL */
+  void* workspace; long long workspace_bytes;        /* mer_fusion_group_workspace_bytes(desc) */
+} mer_fusion_group;
+long long mer_fusion_group_param_count(int Da, int Dt, int Dv, int H, int C1, int C2);
+long long mer_fusion_group_workspace_bytes(const mer_fusion_group* desc);
+/* One whole train (train != 0: forward, CE + MSE, backward, value clipping, Adam) or eval step of the group. */
+int mer_fusion_group_step(const mer_fusion_group* desc, int train, mer_stream_t stream);
+/* keep[r, c] (uint8 [rows, cols]) of the dropout mask the step uses at (seed, step, site) — for inspection / tests. */
+int mer_fusion_group_dropout_mask(uint64_t seed, int step, int site, int rows, int cols, float p, uint8_t* keep,
+                                  mer_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Encoder level                                                                               */
 /* ------------------------------------------------------------------------------------------ */

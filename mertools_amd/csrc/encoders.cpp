@@ -846,6 +846,7 @@ extern "C" int mer_abi_sizeof(const char* name) {
   MER_SZ(mer_bert_weights);
   MER_SZ(mer_videomae_config);
   MER_SZ(mer_videomae_weights);
+  MER_SZ(mer_fusion_group);
 #undef MER_SZ
   return MER_EINVAL;
 }

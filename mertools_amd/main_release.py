@@ -152,14 +152,19 @@ def build_parser():
     p.add_argument('--eager', action='store_true', default=False,
                    help="the reference's loop verbatim (one kernel launch per op, 3-5 host syncs per minibatch) instead of one captured "
                         "HIP graph per minibatch with per-epoch result copies; same results, for bit-comparison")
+    p.add_argument('--parallel_folds', action='store_true', default=False,
+                   help="train the 5 folds of the run as ONE group (mer_fusion_group_step: --model attention --feat_type utt, MER2023 "
+                        "only); same CPU-generator draws as the sequential loop, so at dropout 0 the same results and file names. "
+                        "Dropout masks come from an in-kernel hash seeded by (effective seed, fold): a different draw from the "
+                        "sequential path's. Without --seed the effective seed is drawn from python's random and printed")
+    p.add_argument('--num_trials', type=int, default=None,
+                   help="with --seed s: N hyper-parameter trials, trial t being exactly a --parallel_folds run with --seed s+t; "
+                        "trials with equal hidden_dim train as one group (5 x trials models)")
     return p
 
 
-def main(argv=None):
-    args = build_parser().parse_args(argv)
-    torch.cuda.set_device(args.gpu)
-    if args.data_root:
-        config.set_data_root(args.data_root)
+def _setup(args):
+    """The run preamble of main-release.py (seeding, feature type, save root, hyper-parameter draw, result-name prefix)."""
     if args.seed is not None:
         random.seed(args.seed)
         np.random.seed(args.seed)
@@ -197,6 +202,17 @@ def main(argv=None):
         prefix_name += f'_trainsnr:{args.train_snr}_testsnr:{args.test_snr}'
     if args.fusion_topn is not None:
         prefix_name += f'_fusiontopn:{args.fusion_topn}_modality:{args.fusion_modality}'
+    return args, whole_features, save_resroot, prefix_name
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    if args.parallel_folds or args.num_trials is not None:
+        return main_group(args)
+    torch.cuda.set_device(args.gpu)
+    if args.data_root:
+        config.set_data_root(args.data_root)
+    args, whole_features, save_resroot, prefix_name = _setup(args)
 
     print('====== Reading Data =======')
     dataloader_class = get_dataloaders(args)
@@ -253,13 +269,18 @@ def main(argv=None):
         del model, optimizer, trainer
         torch.cuda.empty_cache()
 
+    _save_results(args, folder_save, folder_duration, dataloader_class, len(test_loaders), save_resroot, prefix_name, name_time)
+    return folder_save
+
+
+def _save_results(args, folder_save, folder_duration, dataloader_class, n_tests, save_resroot, prefix_name, name_time):
     print('====== Prediction and Saving =======')
     args.duration = np.sum(folder_duration)
     cv_result = gain_cv_results(folder_save)
     save_path = f'{save_resroot}/cv_{prefix_name}_{cv_result}_{name_time}.npz'
     print(f'save results in {save_path}')
     np.savez_compressed(save_path, args=np.array(args, dtype=object))
-    for jj in range(len(test_loaders)):
+    for jj in range(n_tests):
         emo_labels, emo_probs = average_folder_for_emos(folder_save, f'test{jj + 1}')
         val_labels, val_preds = average_folder_for_vals(folder_save, f'test{jj + 1}')
         _, test_result = dataloader_class.calculate_results(emo_probs, emo_labels, val_preds, val_labels)
@@ -269,7 +290,190 @@ def main(argv=None):
             np.savez_compressed(save_path, emo_probs=emo_probs, args=np.array(args, dtype=object))
         else:
             np.savez_compressed(save_path, args=np.array(args, dtype=object))
-    return folder_save
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# --parallel_folds / --num_trials: every fold (and trial) of the run in one group (fusion_group.FusionGroupTrainer)
+# ---------------------------------------------------------------------------------------------------------------------
+GROUP_SCOPE = "--model attention --feat_type utt --dataset MER2023 (emotion + valence heads)"
+
+
+def check_group_scope(args):
+    """Raises ValueError unless the run is one the grouped kernels build (checked before anything touches the GPU)."""
+    if args.num_trials is not None:
+        if args.seed is None:
+            raise ValueError("--num_trials needs --seed s (trial t runs with the effective seed s + t)")
+        if args.num_trials < 1:
+            raise ValueError("--num_trials must be >= 1")
+    bad = []
+    if args.model != 'attention':
+        bad.append(f'--model {args.model}')
+    if args.feat_type != 'utt':
+        bad.append(f'--feat_type {args.feat_type}')
+    if args.dataset != 'MER2023' or args.train_dataset is not None or args.test_dataset is not None:
+        bad.append(f'--dataset {args.dataset}')
+    if args.test_snr is not None or args.train_snr is not None or args.fusion_topn is not None or args.eager:
+        bad.append('--train_snr / --test_snr / --fusion_topn / --eager')
+    if bad:
+        raise ValueError(f"--parallel_folds / --num_trials support {GROUP_SCOPE} only, not {', '.join(bad)}")
+
+
+def _base_seed_draw():
+    """The int64 draw DataLoader's iterator makes from the CPU generator when it is constructed (_BaseDataLoaderIter)."""
+    torch.empty((), dtype=torch.int64).random_()
+
+
+def fold_plan(args, folds, n_tests, epochs):
+    """Replays, in order, every CPU-generator draw of main()'s sequential loop: fold f's get_models initialisation right after
+    the draws of folds < f; per epoch the train loader's base-seed draw + SubsetRandomSampler permutation, the same for the eval
+    loader, then the base-seed draws of the test loaders.  Returns (CPU models, orders[f][epoch] = (train rows, eval rows))."""
+    from torch.utils.data.sampler import SubsetRandomSampler
+    models, orders = [], []
+    for tr, ev in folds:
+        models.append(get_models(args))
+        per_epoch = []
+        tr_s, ev_s = SubsetRandomSampler(tr), SubsetRandomSampler(ev)
+        for _ in range(epochs):
+            _base_seed_draw()
+            tr_o = np.array(list(tr_s), dtype=np.int64)
+            _base_seed_draw()
+            ev_o = np.array(list(ev_s), dtype=np.int64)
+            for _ in range(n_tests):
+                _base_seed_draw()
+            per_epoch.append((tr_o, ev_o))
+        orders.append(per_epoch)
+    return models, orders
+
+
+def _batches(order, B):
+    return [order[i:i + B] for i in range(0, len(order), B)]
+
+
+def main_group(args):
+    """--parallel_folds [--num_trials N]: returns the folder_save list of the run (a list of them, one per trial, with --num_trials)."""
+    import copy
+    from .fusion_group import FusionGroupTrainer, dropout_seed
+    check_group_scope(args)
+    torch.cuda.set_device(args.gpu)
+    if args.data_root:
+        config.set_data_root(args.data_root)
+    seed0 = args.seed
+    if seed0 is None:
+        seed0 = random.randint(0, 2 ** 31 - 1)
+        print(f'--parallel_folds: effective seed {seed0} (repeat the run with --seed {seed0})')
+    n_trials = args.num_trials or 1
+    trials, data = [], None
+    for t in range(n_trials):
+        a = copy.deepcopy(args)
+        a.seed = seed0 + t
+        a, _, save_resroot, prefix_name = _setup(a)
+        if data is None:
+            print('====== Reading Data =======')
+            dataloader_class = get_dataloaders(a)
+            train_loaders, eval_loaders, test_loaders = dataloader_class.get_loaders()
+            folds = [(list(tl.sampler.indices), list(el.sampler.indices)) for tl, el in zip(train_loaders, eval_loaders)]
+            sets = [train_loaders[0].dataset] + [tl.dataset for tl in test_loaders]
+            data = dict(cls=dataloader_class, sets=sets, n_tests=len(test_loaders))
+        else:
+            mer = data['cls'].dataloader                                                            # get_loaders' only draw
+            folds = mer.random_split_indexes(len(data['sets'][0]), mer.num_folder)
+            a.output_dim1, a.output_dim2, a.metric_name = mer.args.output_dim1, mer.args.output_dim2, mer.args.metric_name
+        a.audio_dim, a.text_dim, a.video_dim = data['sets'][0].get_featdim()
+        if a.output_dim1 == 0 or a.output_dim2 != 1:
+            raise ValueError(f"--parallel_folds supports {GROUP_SCOPE} only")
+        models, orders = fold_plan(a, folds, data['n_tests'], a.epochs)
+        trials.append(dict(args=a, seed=a.seed, models=models, orders=orders, save_resroot=save_resroot, prefix_name=prefix_name))
+
+    # one table for every split: train rows, then each test set's rows (the float32 values Data_Feat.collater hands over)
+    cols = [s.collater([s[i] for i in range(len(s))]) for s in data['sets']]
+    offs = np.cumsum([0] + [len(s) for s in data['sets']])
+    names = sum((c[3] for c in cols), [])
+    emo_all = torch.cat([c[1] for c in cols]).numpy()
+    val_all = torch.cat([c[2] for c in cols]).numpy()
+    tables = [torch.cat([c[0][k] for c in cols]) for k in ('audios', 'texts', 'videos')]
+
+    by_h = {}
+    for t, tr in enumerate(trials):
+        by_h.setdefault(tr['args'].hidden_dim, []).append(t)
+    for h, members in by_h.items():
+        _train_group([trials[t] for t in members], data, tables, emo_all, val_all, names, offs, FusionGroupTrainer, dropout_seed)
+    outs = [tr['folder_save'] for tr in trials]
+    return outs if args.num_trials is not None else outs[0]
+
+
+def _train_group(trials, data, tables, emo_all, val_all, names, offs, FusionGroupTrainer, dropout_seed):
+    dataloader_class, n_tests = data['cls'], data['n_tests']
+    a0 = trials[0]['args']
+    B, epochs = a0.batch_size, a0.epochs
+    members = [(tr, f) for tr in trials for f in range(len(tr['models']))]
+    G = len(members)
+    print(f'====== Training and Evaluation: {G} models (hidden_dim {a0.hidden_dim}) in one group =======')
+    start_time = time.time()
+    models = [tr['models'][f].cuda() for tr, f in members]
+    trainer = FusionGroupTrainer(models, lr=[tr['args'].lr for tr, _ in members], weight_decay=[tr['args'].l2 for tr, _ in members],
+                                 grad_clip=[m.model.grad_clip for m in models],
+                                 seeds=[dropout_seed(tr['seed'], f) for tr, f in members], batch_size=B)
+    trainer.set_tables(*tables, emo_all, val_all)
+    tests = [np.arange(offs[j + 1], offs[j + 2]) for j in range(n_tests)]
+    stores = [[] for _ in range(G)]
+    metrics = [[] for _ in range(G)]
+    for epoch in range(epochs):
+        # phases in the sequential loop's order: train, eval, test1..; each model's minibatches, padded with idle steps
+        phases = [[_batches(tr['orders'][f][epoch][0], B) for tr, f in members],
+                  [_batches(tr['orders'][f][epoch][1], B) for tr, f in members]]
+        phases += [[_batches(rows, B)] * G for rows in tests]
+        steps = [max(len(b) for b in ph) for ph in phases]
+        S = sum(steps)
+        index = np.zeros((S, G, B), dtype=np.int32)
+        count = np.zeros((S, G), dtype=np.int32)
+        s0 = 0
+        for ph, n in zip(phases, steps):
+            for g in range(G):
+                for i, rows in enumerate(ph[g]):
+                    index[s0 + i, g, :len(rows)] = rows
+                    count[s0 + i, g] = len(rows)
+            s0 += n
+        loss, emo, val = trainer.run(index, count, [True] * steps[0] + [False] * (S - steps[0]))
+        loss, emo, val = loss.cpu().numpy(), emo.cpu().numpy(), val.cpu().numpy()
+        s0 = 0
+        results = []
+        for ph, n in zip(phases, steps):
+            res_g = []
+            for g in range(G):
+                nb = len(ph[g])
+                rows = np.concatenate(ph[g]) if nb else np.zeros(0, dtype=np.int64)
+                cnt = count[s0:s0 + nb, g]
+                probs = np.concatenate([emo[s0 + i, g, :c] for i, c in enumerate(cnt)])
+                vpred = np.concatenate([val[s0 + i, g, :c] for i, c in enumerate(cnt)]).reshape(-1, 1)
+                res, _ = dataloader_class.calculate_results(probs, emo_all[rows], vpred, val_all[rows])
+                res_g.append(dict(names=[names[r] for r in rows], loss=np.mean(np.ascontiguousarray(loss[s0:s0 + nb, g])), **res))
+            results.append(res_g)
+            s0 += n
+        for g, (tr, f) in enumerate(members):
+            a = tr['args']
+            epoch_store = {}
+            func_update_storage(results[1][g], 'eval', epoch_store)
+            train_metric = gain_metric_from_results(results[0][g], a.metric_name)
+            eval_metric = gain_metric_from_results(results[1][g], a.metric_name)
+            metrics[g].append(eval_metric)
+            print('seed:%d; folder:%d; epoch:%d; metric:%s; train results:%.4f; eval results:%.4f'
+                  % (tr['seed'], f + 1, epoch + 1, a.metric_name, train_metric, eval_metric))
+            for jj in range(n_tests):
+                func_update_storage(results[2 + jj][g], f'test{jj + 1}', epoch_store)
+            stores[g].append(epoch_store)
+    duration = time.time() - start_time
+    for tr in trials:
+        tr['folder_save'] = []
+    for g, (tr, f) in enumerate(members):
+        best_index = np.argmax(np.array(metrics[g]))
+        tr['folder_save'].append(stores[g][best_index])
+        print(f'>>>>> Finish: seed {tr["seed"]}, folder {f + 1}, best_index: {best_index} >>>>>')
+    for tr in trials:
+        n_f = len(tr['folder_save'])
+        _save_results(tr['args'], tr['folder_save'], [duration * n_f / G] * n_f, dataloader_class, n_tests, tr['save_resroot'],
+                      tr['prefix_name'], time.time())
+    del trainer, models
+    torch.cuda.empty_cache()
 
 
 if __name__ == '__main__':

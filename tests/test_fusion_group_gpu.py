@@ -1,0 +1,317 @@
+"""Grouped fusion training (csrc/fusion_group.hip, mertools_amd.fusion_group, main_release --parallel_folds / --num_trials) on the
+GPU: the reference's golden steps, bitwise equality with FusionGraphTrainer at dropout 0, group invariance (position, idle models,
+group size), the counter-based dropout masks, eval steps and the CLI against the default sequential path."""
+import argparse
+import copy
+import os
+import random
+
+import numpy as np
+import pytest
+import torch
+
+from util import assert_close
+
+pytestmark = pytest.mark.gpu
+G_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+M64 = 0xFFFFFFFFFFFFFFFF
+
+
+def _args(H=64, dropout=0.0, dims=(96, 80, 64), grad_clip=-1.0):
+    return argparse.Namespace(model="attention", audio_dim=dims[0], text_dim=dims[1], video_dim=dims[2], output_dim1=6, output_dim2=1,
+                              dropout=dropout, hidden_dim=H, grad_clip=grad_clip, feat_type="utt")
+
+
+def _models(dev, n, seed, **kw):
+    from mertools_amd.toolkit.models import get_models
+    torch.manual_seed(seed)
+    return [get_models(_args(**kw)).to(dev) for _ in range(n)]
+
+
+def _tables(n, dims=(96, 80, 64), seed=0):
+    g = torch.Generator().manual_seed(seed)
+    return (torch.randn(n, dims[0], generator=g), torch.randn(n, dims[1], generator=g), torch.randn(n, dims[2], generator=g),
+            torch.randint(0, 6, (n,), generator=g), (torch.rand(n, generator=g) * 6 - 3))
+
+
+def _batch(tab, rows, dev):
+    a, t, v, e, val = tab
+    rows = torch.as_tensor(rows, dtype=torch.long)
+    return {"audios": a[rows].to(dev), "texts": t[rows].to(dev), "videos": v[rows].to(dev)}, e[rows].to(dev), val[rows].to(dev)
+
+
+def _schedule(G, S, B, N, seed, partial=()):
+    rng = np.random.RandomState(seed)
+    index = rng.randint(0, N, size=(S, G, B)).astype(np.int32)
+    count = np.full((S, G), B, dtype=np.int32)
+    for g, n in partial:
+        count[S - 1, g] = n
+    return index, count
+
+
+def test_group_matches_golden_reference(dev):
+    """A G=3 group, every slot loaded with tests/golden/fusion_attention.npz's init_* and fed its 5 minibatches (lr 1e-3, wd 1e-5):
+    the reference's losses and final parameters, at test_graph_trainer_matches_reference's tolerances."""
+    from mertools_amd.fusion_group import FusionGroupTrainer
+    g = np.load(os.path.join(G_DIR, "fusion_attention.npz"))
+    ms = _models(dev, 3, 0)
+    for m in ms:
+        m.model.load_state_dict({k: torch.from_numpy(g["init_" + k]) for k in m.model.state_dict()})
+    S, B = g["x_audios"].shape[:2]
+    tab = [torch.from_numpy(g["x_" + k]).reshape(S * B, -1) for k in ("audios", "texts", "videos")]
+    tr = FusionGroupTrainer(ms, lr=1e-3, weight_decay=1e-5, grad_clip=-1.0, batch_size=B)
+    tr.set_tables(*tab, torch.from_numpy(g["emos"]).reshape(-1), torch.from_numpy(g["vals"]).reshape(-1))
+    index = np.tile((np.arange(S)[:, None] * B + np.arange(B)[None, :])[:, None, :], (1, 3, 1)).astype(np.int32)
+    loss, _, _ = tr.run(index, np.full((S, 3), B, dtype=np.int32), True)
+    loss = loss.cpu().numpy()
+    for k in range(3):
+        np.testing.assert_allclose(loss[:, k], g["losses"], rtol=5e-5)
+        for name, p in ms[k].model.state_dict().items():
+            assert_close(p.cpu(), torch.from_numpy(g["final_" + name]), 1e-4, f"slot {k} final {name}")
+
+
+def test_group_bitwise_equals_graph_trainer_at_dropout_0(dev):
+    """Three models (different inits and lrs, one with grad_clip > 0), different minibatches, 20 steps, partial last batches:
+    losses, outputs and final parameters are torch.equal to FusionGraphTrainer's on the same minibatches."""
+    from mertools_amd.fusion_group import FusionGroupTrainer
+    from mertools_amd.fusion_trainer import FusionGraphTrainer
+    G, S, B, N = 3, 20, 16, 300
+    ms = [_models(dev, 1, 10 + k, grad_clip=c)[0] for k, c in enumerate((-1.0, 0.05, -1.0))]
+    refs = [copy.deepcopy(m) for m in ms]
+    lrs, wds, clips = [1e-3, 3e-3, 5e-4], [1e-5, 0.0, 1e-4], [-1.0, 0.05, -1.0]
+    tab = _tables(N)
+    index, count = _schedule(G, S, B, N, 1, partial=[(0, 5), (1, 11)])
+    tr = FusionGroupTrainer(ms, lr=lrs, weight_decay=wds, grad_clip=clips, batch_size=B)
+    tr.set_tables(*tab)
+    loss, emo, val = (x.clone() for x in tr.run(index, count, True))
+    for k in range(G):
+        ref = FusionGraphTrainer(refs[k], lr=lrs[k], weight_decay=wds[k], grad_clip=clips[k])
+        for s in range(S):
+            n = int(count[s, k])
+            batch, e, v = _batch(tab, index[s, k, :n], dev)
+            rl, re_, rv = ref.train_step(batch, e, v)
+            assert torch.equal(loss[s, k], rl), (k, s, loss[s, k].item(), rl.item())
+            assert torch.equal(emo[s, k, :n], re_), (k, s)
+            assert torch.equal(val[s, k, :n], rv.view(-1)), (k, s)
+        for (name, p), (_, q) in zip(ms[k].state_dict().items(), refs[k].state_dict().items()):
+            assert torch.equal(p, q), (k, name)
+        assert torch.equal(tr.m[k], ref.opt.m) and torch.equal(tr.v[k], ref.opt.v) and int(tr.step[k]) == int(ref.opt.step_dev) == S
+
+
+def _run_group(dev, inits, order, index, count, seeds, p):
+    from mertools_amd.fusion_group import FusionGroupTrainer
+    ms = [copy.deepcopy(inits[i]) for i in order]
+    tr = FusionGroupTrainer(ms, lr=[1e-3 * (1 + i) for i in order], weight_decay=1e-5, grad_clip=[0.1 if i % 2 else -1.0 for i in order],
+                            seeds=[seeds[i] for i in order], batch_size=index.shape[2])
+    tr.set_tables(*_tables(200, seed=3))
+    loss, emo, val = (x.clone() for x in tr.run(index, count, True))
+    return tr, loss, emo, val
+
+
+def test_group_invariance_with_dropout(dev):
+    """Six models at dropout 0.3: one group, six groups of one, and a permuted group in which models sit idle at some steps give
+    each model bitwise the same losses, outputs, gradients, parameters, Adam moments and step counter; an idle step touches nothing."""
+    G, S, B = 6, 8, 12
+    inits = [_models(dev, 1, 20 + k, dropout=0.3)[0] for k in range(G)]
+    seeds = [(0x1234567 * (k + 1)) & M64 for k in range(G)]
+    index, count = _schedule(G, S, B, 200, 5, partial=[(2, 7), (4, 1)])
+    tr_a, la, ea, va = _run_group(dev, inits, list(range(G)), index, count, seeds, 0.3)
+    singles = [_run_group(dev, inits, [k], index[:, k:k + 1], count[:, k:k + 1], seeds, 0.3) for k in range(G)]
+    perm = [3, 0, 5, 1, 4, 2]
+    rng = np.random.RandomState(9)
+    idle = {pos: set(rng.choice(S + 3, 3, replace=False).tolist()) for pos in range(G)}
+    index_c = np.zeros((S + 3, G, B), dtype=np.int32)
+    count_c = np.zeros((S + 3, G), dtype=np.int32)
+    where = {}
+    for pos, k in enumerate(perm):
+        act = [s for s in range(S + 3) if s not in idle[pos]]
+        for i, s in enumerate(act):
+            index_c[s, pos], count_c[s, pos] = index[i, k], count[i, k]
+        where[k] = (pos, act)
+    tr_c, lc, ec, vc = _run_group(dev, inits, perm, index_c, count_c, seeds, 0.3)
+    for k in range(G):
+        tr_s, ls, es, vs = singles[k]
+        pos, act = where[k]
+        for i in range(S):
+            n = int(count[i, k])
+            for (l2, e2, v2, g2) in ((ls, es, vs, 0), (lc, ec, vc, None)):
+                s2 = i if g2 == 0 else act[i]
+                gg = 0 if g2 == 0 else pos
+                assert torch.equal(la[i, k], l2[s2, gg]), (k, i)
+                assert torch.equal(ea[i, k, :n], e2[s2, gg, :n]) and torch.equal(va[i, k, :n], v2[s2, gg, :n]), (k, i)
+        for x in ("flat", "flat_grad", "m", "v", "step"):
+            a = getattr(tr_a, x)[k]
+            assert torch.equal(a, getattr(tr_s, x)[0]) and torch.equal(a, getattr(tr_c, x)[pos]), (k, x)
+    # an idle step leaves a model's parameters, gradients, moments and counter alone while the others train
+    before = {x: getattr(tr_c, x).clone() for x in ("flat", "flat_grad", "m", "v", "step")}
+    cnt = np.full((1, G), B, dtype=np.int32)
+    cnt[0, 1] = 0
+    tr_c.run(index_c[:1], cnt, True)
+    for x, b in before.items():
+        assert torch.equal(getattr(tr_c, x)[1], b[1]), x
+        assert not torch.equal(getattr(tr_c, x)[0], b[0]), x
+
+
+def _np_mask(seed, step, site, rows, cols, p):
+    """The documented hash of csrc/fusion_group.hip, restated in numpy."""
+    with np.errstate(over="ignore"):
+        r = np.arange(rows, dtype=np.uint64)[:, None]
+        c = np.arange(cols, dtype=np.uint64)[None, :]
+        ctr = (np.uint64(step & 0xFFFFFFFF) << np.uint64(32)) | (np.uint64(site) << np.uint64(30)) | (r << np.uint64(16)) | c
+        z = np.uint64(seed) + (ctr + np.uint64(1)) * np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    u = (z >> np.uint64(40)).astype(np.float32) * np.float32(2.0 ** -24)
+    return (u >= np.float32(p)).astype(np.uint8)
+
+
+def test_dropout_mask_is_the_documented_hash(dev):
+    from mertools_amd.fusion_group import dropout_mask
+    for seed, step, site, p in ((0, 0, 0, 0.3), (0xDEADBEEFCAFEF00D, 7, 2, 0.5), (12345, 1 << 20, 3, 0.2)):
+        got = dropout_mask(seed, step, site, 33, 300, p, dev).cpu().numpy()
+        assert np.array_equal(got, _np_mask(seed, step, site, 33, 300, p)), (seed, step, site)
+    big = dropout_mask(99, 3, 1, 256, 512, 0.3, dev).float().mean().item()
+    assert abs(big - 0.7) < 0.01, big
+    base = dropout_mask(1, 2, 0, 32, 128, 0.4, dev)
+    for other in (dropout_mask(2, 2, 0, 32, 128, 0.4, dev), dropout_mask(1, 3, 0, 32, 128, 0.4, dev), dropout_mask(1, 2, 1, 32, 128, 0.4, dev)):
+        assert not torch.equal(base, other)
+
+
+def test_dropout_training_matches_cpu_composition(dev):
+    """3 train steps at p = 0.3 against a CPU composition of the oracle's pieces with the same masks (x * keep / (1 - p) at the
+    three encoder inputs and the attention_mlp input): losses and parameters within 1e-4."""
+    import torch.nn.functional as F
+    from oracle import fusion_ref as R
+    from mertools_amd.fusion_group import FusionGroupTrainer, dropout_mask
+    p, B, S, seed = 0.3, 16, 3, 0xABCDEF
+    m = _models(dev, 1, 31, dropout=p, dims=(40, 24, 32), H=32)[0]
+    sd = {k: v.detach().cpu().clone() for k, v in m.model.state_dict().items()}
+    tab = _tables(64, dims=(40, 24, 32), seed=4)
+    tr = FusionGroupTrainer([m], lr=1e-3, weight_decay=1e-5, grad_clip=-1.0, seeds=[seed], batch_size=B)
+    tr.set_tables(*tab)
+    index, count = _schedule(1, S, B, 64, 2, partial=[(0, 9)])
+    loss = tr.run(index, count, True)[0].cpu().numpy()[:, 0]
+    scale = np.float32(1.0) / (np.float32(1.0) - np.float32(p))
+    ms = {k: torch.zeros_like(v) for k, v in sd.items()}
+    vs = {k: torch.zeros_like(v) for k, v in sd.items()}
+    for s in range(S):
+        n = int(count[s, 0])
+        rows = torch.as_tensor(index[s, 0, :n], dtype=torch.long)
+        xs = [tab[i][rows] for i in range(3)]
+        keeps = [dropout_mask(seed, s, site, n, w, p, dev).cpu().float() for site, w in enumerate([40, 24, 32, 96])]
+        prm = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
+        enc = [R.mlp_encoder(prm, name, xs[i] * keeps[i] * scale) for i, name in enumerate(("audio_encoder", "text_encoder", "video_encoder"))]
+        mh = torch.cat(enc, dim=1)
+        att = F.linear(R.mlp_encoder(prm, "attention_mlp", mh * keeps[3] * scale), prm["fc_att.weight"], prm["fc_att.bias"])
+        fused = torch.matmul(torch.stack(enc, dim=2), att.unsqueeze(2)).squeeze(2)
+        e = F.linear(fused, prm["fc_out_1.weight"], prm["fc_out_1.bias"])
+        v = F.linear(fused, prm["fc_out_2.weight"], prm["fc_out_2.bias"])
+        ref_loss = R.ce_loss(e, tab[3][rows]) + R.mse_loss(v, tab[4][rows])
+        grads = torch.autograd.grad(ref_loss, list(prm.values()))
+        with torch.no_grad():
+            for (k, w), g in zip(list(prm.items()), grads):
+                sd[k], ms[k], vs[k] = R.adam_step(w.detach(), g, ms[k], vs[k], s + 1, lr=1e-3, wd=1e-5)
+        assert abs(loss[s] - ref_loss.item()) <= 1e-4 * max(1.0, abs(ref_loss.item())), (s, loss[s], ref_loss.item())
+    for k, w in m.model.state_dict().items():
+        assert_close(w.cpu(), sd[k], 1e-4, f"dropout final {k}")
+
+
+def test_eval_step_bitwise_equals_graph_trainer(dev):
+    from mertools_amd.fusion_group import FusionGroupTrainer
+    from mertools_amd.fusion_trainer import FusionGraphTrainer
+    G, B = 2, 16
+    ms = [_models(dev, 1, 40 + k, dropout=0.3)[0] for k in range(G)]
+    refs = [FusionGraphTrainer(copy.deepcopy(m), lr=1e-3) for m in ms]
+    tab = _tables(100, seed=6)
+    tr = FusionGroupTrainer(ms, lr=1e-3, weight_decay=0.0, grad_clip=-1.0, batch_size=B)
+    tr.set_tables(*tab)
+    index, count = _schedule(G, 2, B, 100, 7, partial=[(1, 3)])
+    before = (tr.flat.clone(), tr.m.clone(), tr.v.clone(), tr.step.clone())
+    loss, emo, val = (x.clone() for x in tr.run(index, count, False))
+    for x, b in zip((tr.flat, tr.m, tr.v, tr.step), before):
+        assert torch.equal(x, b)
+    for k in range(G):
+        for s in range(2):
+            n = int(count[s, k])
+            batch, e, v = _batch(tab, index[s, k, :n], dev)
+            rl, re_, rv = refs[k].eval_step(batch, e, v)
+            assert torch.equal(loss[s, k], rl) and torch.equal(emo[s, k, :n], re_) and torch.equal(val[s, k, :n], rv.view(-1)), (k, s)
+
+
+def _corpus(tmp_path, seed=1):
+    root = tmp_path / "data" / "mer2023-dataset-process"
+    rng = np.random.RandomState(seed)
+    names = {"train": [f"tr_{i:03d}" for i in range(50)], "test1": [f"t1_{i:02d}" for i in range(9)],
+             "test2": [f"t2_{i:02d}" for i in range(7)], "test3": [f"t3_{i:02d}" for i in range(5)]}
+    emos = ['neutral', 'angry', 'happy', 'sad', 'worried', 'surprise']
+    corp = {}
+    for split, ns in names.items():
+        corp[f"{split}_corpus"] = {n: {"emo": emos[rng.randint(6)], "val": float(rng.uniform(-3, 3))} for n in ns}
+        if split == "test3":
+            for n in ns:
+                del corp[f"{split}_corpus"][n]["val"]
+    os.makedirs(root / "features", exist_ok=True)
+    np.savez_compressed(root / "label-6way.npz", **{k: np.array(v, dtype=object) for k, v in corp.items()})
+    for feat, d in {"audio-UTT": 24, "text-UTT": 16, "video-UTT": 20}.items():
+        os.makedirs(root / "features" / feat, exist_ok=True)
+        for ns in names.values():
+            for n in ns:
+                np.save(root / "features" / feat / f"{n}.npy", rng.randn(d).astype(np.float32))
+    return ["--model", "attention", "--feat_type", "utt", "--dataset", "MER2023", "--audio_feature", "audio-UTT", "--text_feature", "text-UTT",
+            "--video_feature", "video-UTT", "--batch_size", "16", "--gpu", "0", "--data_root", str(tmp_path / "data")]
+
+
+def _same_store(a_list, b_list):
+    assert len(a_list) == len(b_list)
+    for a, b in zip(a_list, b_list):
+        assert set(a) == set(b)
+        for k in a:
+            if isinstance(a[k], np.ndarray):
+                assert a[k].dtype == b[k].dtype and np.array_equal(a[k], b[k]), k
+            else:
+                assert a[k] == b[k], k
+
+
+def _files(d):
+    return sorted(f.rsplit("_", 1)[0] for f in os.listdir(d))
+
+
+def test_main_release_parallel_folds_equals_default_path(dev, tmp_path):
+    from mertools_amd import main_release
+    base = _corpus(tmp_path) + ["--epochs", "3", "--seed", "3"]
+    hyper = tmp_path / "tune.yaml"
+    hyper.write_text("attention:\n  hidden_dim: 64\n  dropout: 0.0\n  grad_clip: 1.0\n  lr: 1.0e-3\n")
+    res_d = main_release.main(base + ["--hyper_path", str(hyper), "--save_root", str(tmp_path / "seq")])
+    res_p = main_release.main(base + ["--hyper_path", str(hyper), "--save_root", str(tmp_path / "par"), "--parallel_folds"])
+    _same_store(res_d, res_p)
+    assert _files(tmp_path / "seq-trimodal" / "result") == _files(tmp_path / "par-trimodal" / "result")
+    hyper.write_text("attention:\n  hidden_dim: 64\n  dropout: 0.3\n  grad_clip: -1\n  lr: 1.0e-3\n")
+    r1 = main_release.main(base + ["--hyper_path", str(hyper), "--save_root", str(tmp_path / "d1"), "--parallel_folds"])
+    r2 = main_release.main(base + ["--hyper_path", str(hyper), "--save_root", str(tmp_path / "d2"), "--parallel_folds"])
+    _same_store(r1, r2)
+    for fold in r1:
+        for k, x in fold.items():
+            if isinstance(x, np.ndarray) and x.dtype.kind == "f":
+                assert np.isfinite(x).all(), k
+
+
+def test_main_release_num_trials_equals_default_runs(dev, tmp_path, monkeypatch):
+    """--num_trials 3 --seed s with hidden_dim drawn from [64, 128] (at least two groups form): trial t's stored arrays equal a
+    default-path run with --seed s+t."""
+    import yaml
+    from mertools_amd import main_release
+    from mertools_amd.toolkit.utils.functions import func_random_select
+    tune = {"attention": {"hidden_dim": [64, 128], "dropout": [0.0], "grad_clip": [1.0], "lr": [1.0e-3]}}
+    monkeypatch.setattr(yaml, "safe_load", lambda fh: copy.deepcopy(tune))
+
+    def drawn(seed):
+        random.seed(seed)
+        return func_random_select(copy.deepcopy(tune["attention"]))["hidden_dim"]
+    s = next(s for s in range(100) if len({drawn(s + t) for t in range(3)}) == 2)
+    base = _corpus(tmp_path, seed=2) + ["--epochs", "2"]
+    res_t = main_release.main(base + ["--num_trials", "3", "--seed", str(s), "--save_root", str(tmp_path / "trials")])
+    assert len(res_t) == 3
+    for t in range(3):
+        res_d = main_release.main(base + ["--seed", str(s + t), "--save_root", str(tmp_path / f"seq{t}")])
+        _same_store(res_d, res_t[t])

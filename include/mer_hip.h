@@ -253,6 +253,12 @@ int mer_vit_patchify(const float* pixels, int N, int C, int H, int W, int P, voi
  * (c, dt, i, j) order of the flattened Conv3d weight (HF:videomae/modeling_videomae.py:119-176). */
 int mer_video_patchify(const float* pixels, int B, int F, int C, int H, int W, int P, int ts, void* out_hi, void* out_lo,
                        int dtype, mer_stream_t stream);
+/* The same tubelet planes from u8 frames: table device u8 [n_table, S, S, 3] of already-resized frames in stored byte order (channel c
+ * is byte c: no swap), frame_idx device int32 [B, F] = the table row of each frame of each view, mean3 / std3 host float[3].  Pixel =
+ * (float(u) / 255 - mean3[c]) / std3[c] in fp32 with true division, so the planes equal mer_video_patchify's of those fp32 pixels bit for
+ * bit; no [B, F, 3, S, S] fp32 tensor is built.  Rows outside [0, n_table) are not read (their pixels are NaN).  table 4-byte aligned. */
+int mer_video_patchify_u8(const unsigned char* table, int n_table, int S, const int* frame_idx, int B, int F, const float* mean3,
+                          const float* std3, int P, int ts, void* out_hi, void* out_lo, int dtype, mer_stream_t stream);
 /* x[r,:] += pos[r % P,:] in place (fixed sin-cos position table). */
 int mer_add_pos(float* x, const float* pos, long long rows, int P, int D, mer_stream_t stream);
 
@@ -582,6 +588,13 @@ long long mer_videomae_workspace_bytes(const mer_videomae* h, int B);
 int mer_videomae_forward(const mer_videomae* h, const float* pixels, int B, void* workspace, long long workspace_bytes,
                          float* last_hidden_state, const int* seg_start, const int* seg_len, int nseg, float* pooled,
                          mer_stream_t stream);
+
+/* mer_videomae_forward with mer_video_patchify_u8 in front: view b's frames are table rows frame_idx[b, 0..F-1] (device int32 [B, F]),
+ * table device u8 [n_table, image_size, image_size, channels == 3].  Same workspace as mer_videomae_forward(h, B), same outputs. */
+int mer_videomae_forward_frames(const mer_videomae* h, const unsigned char* table, int n_table, const int* frame_idx, int B,
+                                const float* mean3, const float* std3, void* workspace, long long workspace_bytes,
+                                float* last_hidden_state, const int* seg_start, const int* seg_len, int nseg, float* pooled,
+                                mer_stream_t stream);
 
 /* ---- BERT / RoBERTa text encoder ------------------------------------------------------------
  * Replaces `model(**inputs, output_hidden_states=True).hidden_states` at

@@ -163,6 +163,8 @@ _PROTOS = {
     "mer_posconv_pack": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "mer_vit_patchify": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "mer_video_patchify": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "mer_video_patchify_u8": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                      c_int, c_void_p]),
     "mer_add_pos": (c_int, [c_void_p, c_void_p, c_ll, c_int, c_int, c_void_p]),
     "mer_vit_assemble": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int,
                                  c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
@@ -232,6 +234,8 @@ _PROTOS = {
     "mer_videomae_workspace_bytes": (c_ll, [c_void_p, c_int]),
     "mer_videomae_forward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_int,
                                      c_void_p, c_void_p]),
+    "mer_videomae_forward_frames": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_ll, c_void_p,
+                                            c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "mer_bert_create": (c_int, [C.POINTER(BertConfig), C.POINTER(BertWeights), C.POINTER(c_void_p)]),
     "mer_bert_destroy": (None, [c_void_p]),
     "mer_bert_workspace_bytes": (c_ll, [c_void_p, c_int, c_int, c_int]),

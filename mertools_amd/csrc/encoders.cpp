@@ -720,25 +720,16 @@ extern "C" long long mer_videomae_workspace_bytes(const mer_videomae* h, int B) 
   return vmae_plan(h, ar, B, p) + 256;
 }
 
-extern "C" int mer_videomae_forward(const mer_videomae* h, const float* pixels, int B, void* workspace, long long workspace_bytes,
-                                    float* last_hidden_state, const int* seg_start, const int* seg_len, int nseg, float* pooled,
-                                    mer_stream_t stream) {
-  MER_REQUIRE(h && pixels && workspace && B > 0, MER_EINVAL, "mer_videomae_forward: bad argument");
-  MER_REQUIRE(((uintptr_t)workspace & 255) == 0, MER_EINVAL, "mer_videomae_forward: workspace must be 256-byte aligned");
+// the shared tail of both entry points, behind the tubelet planes in p.patches: patch GEMM (Conv3d stride == kernel, bias) + fixed sin-cos
+// positions, the blocks, the final LayerNorm, the per-segment pooling
+static int vmae_tail(const mer_videomae* h, VmaePlan& p, int B, float* last_hidden_state, const int* seg_start, const int* seg_len, int nseg,
+                     float* pooled, hipStream_t st) {
   const mer_videomae_config& c = h->cfg;
   const mer_videomae_weights& w = h->w;
-  hipStream_t st = (hipStream_t)stream;
-  Arena ar(workspace, workspace_bytes, false);
-  VmaePlan p;
-  vmae_plan(h, ar, B, p);
-  MER_REQUIRE(ar.ok(), MER_ENOMEM, "mer_videomae_forward: workspace too small (%lld < %lld bytes)", workspace_bytes, ar.off);
   const int g = c.image_size / c.patch_size, NP = g * g * (c.num_frames / c.tubelet_size), D = c.tf.hidden;
   const int cols = c.channels * c.tubelet_size * c.patch_size * c.patch_size, dt = c.tf.dtype, ps = c.tf.passes;
   const P16 none = {nullptr, nullptr};
   float* x = last_hidden_state ? last_hidden_state : p.x;
-  // tubelet embedding: Conv3d(stride == kernel, bias) == GEMM over tubelet rows; + fixed sin-cos positions
-  MER_TRY(mer_video_patchify(pixels, B, c.num_frames, c.channels, c.image_size, c.image_size, c.patch_size, c.tubelet_size,
-                             p.patches.hi, p.patches.lo, dt, st));
   const CorrWs pcw = {&p.tf.corr, NP, nullptr, 0};
   MER_TRY(gemm(st, dt, ps, B * NP, D, cols, p.patches, cols, w.patch_w, w.patch_b, MER_ACT_NONE, nullptr, 0, x, D, none, 0, &pcw));
   MER_TRY(mer_add_pos(x, w.pos, (long long)B * NP, NP, D, st));
@@ -749,6 +740,42 @@ extern "C" int mer_videomae_forward(const mer_videomae* h, const float* pixels, 
     MER_TRY(mer_layernorm(x, D, w.final_ln_g, w.final_ln_b, c.tf.ln_eps, B * NP, D, MER_ACT_NONE, x, D, nullptr, nullptr, 0, dt, st));
   if (pooled) MER_TRY(mer_sum_pool(x, nullptr, nullptr, nullptr, (long long)B * NP, D, nullptr, seg_start, seg_len, nseg, pooled, st));
   return MER_OK;
+}
+
+extern "C" int mer_videomae_forward(const mer_videomae* h, const float* pixels, int B, void* workspace, long long workspace_bytes,
+                                    float* last_hidden_state, const int* seg_start, const int* seg_len, int nseg, float* pooled,
+                                    mer_stream_t stream) {
+  MER_REQUIRE(h && pixels && workspace && B > 0, MER_EINVAL, "mer_videomae_forward: bad argument");
+  MER_REQUIRE(((uintptr_t)workspace & 255) == 0, MER_EINVAL, "mer_videomae_forward: workspace must be 256-byte aligned");
+  const mer_videomae_config& c = h->cfg;
+  hipStream_t st = (hipStream_t)stream;
+  Arena ar(workspace, workspace_bytes, false);
+  VmaePlan p;
+  vmae_plan(h, ar, B, p);
+  MER_REQUIRE(ar.ok(), MER_ENOMEM, "mer_videomae_forward: workspace too small (%lld < %lld bytes)", workspace_bytes, ar.off);
+  // tubelet embedding: Conv3d(stride == kernel, bias) == GEMM over tubelet rows; + fixed sin-cos positions
+  MER_TRY(mer_video_patchify(pixels, B, c.num_frames, c.channels, c.image_size, c.image_size, c.patch_size, c.tubelet_size,
+                             p.patches.hi, p.patches.lo, c.tf.dtype, st));
+  return vmae_tail(h, p, B, last_hidden_state, seg_start, seg_len, nseg, pooled, st);
+}
+
+extern "C" int mer_videomae_forward_frames(const mer_videomae* h, const unsigned char* table, int n_table, const int* frame_idx, int B,
+                                           const float* mean3, const float* std3, void* workspace, long long workspace_bytes,
+                                           float* last_hidden_state, const int* seg_start, const int* seg_len, int nseg, float* pooled,
+                                           mer_stream_t stream) {
+  MER_REQUIRE(h && table && frame_idx && mean3 && std3 && workspace && B > 0 && n_table > 0, MER_EINVAL,
+              "mer_videomae_forward_frames: bad argument");
+  MER_REQUIRE(((uintptr_t)workspace & 255) == 0, MER_EINVAL, "mer_videomae_forward_frames: workspace must be 256-byte aligned");
+  const mer_videomae_config& c = h->cfg;
+  MER_REQUIRE(c.channels == 3, MER_EUNSUPPORTED, "mer_videomae_forward_frames: u8 frames carry 3 channels (model has %d)", c.channels);
+  hipStream_t st = (hipStream_t)stream;
+  Arena ar(workspace, workspace_bytes, false);
+  VmaePlan p;
+  vmae_plan(h, ar, B, p);
+  MER_REQUIRE(ar.ok(), MER_ENOMEM, "mer_videomae_forward_frames: workspace too small (%lld < %lld bytes)", workspace_bytes, ar.off);
+  MER_TRY(mer_video_patchify_u8(table, n_table, c.image_size, frame_idx, B, c.num_frames, mean3, std3, c.patch_size, c.tubelet_size,
+                                p.patches.hi, p.patches.lo, c.tf.dtype, st));
+  return vmae_tail(h, p, B, last_hidden_state, seg_start, seg_len, nseg, pooled, st);
 }
 
 // =============================================================================================

@@ -2,6 +2,7 @@
 //   mer_hubert_conv0_gn  Conv1d(1->C,k,s) + GroupNorm(C,C) + GELU     HF:hubert/modeling_hubert.py:154-175
 //   mer_posconv_pack     group-major zero-padded copy for the grouped positional conv     HF:...:45-92
 //   mer_vit_patchify     NCHW pixels -> [patch, c*P*P] rows (Conv2d stride==kernel as a GEMM)
+//   mer_video_patchify_u8  u8 frame table + per-view frame index -> normalised tubelet rows (gather, normalise, split)
 //   mer_split16          fp32 -> 16-bit hi/lo planes
 //   mer_sum_pool         last-4 hidden-state sum + per-clip temporal mean
 //                        (extract_audio_huggingface.py:98-108, extract_text_huggingface.py:226-249)
@@ -312,6 +313,57 @@ __global__ void video_patchify_kernel(const float* px, int B, int F, int C, int 
     const long long b = bt / nt;
     const int py = pp / gw, pxx = pp % gw;
     const f32x4 v = *reinterpret_cast<const f32x4*>(px + (((b * F + tt * ts + dt) * C + c) * H + (py * P + ii)) * (long long)W + pxx * P + j);
+    typename T16<T>::v4 h, l;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      T hh, ll;
+      split16<T>(v[q], hh, ll);
+      h[q] = hh;
+      l[q] = ll;
+    }
+    *reinterpret_cast<typename T16<T>::v4*>(ohi + e) = h;
+    if (olo) *reinterpret_cast<typename T16<T>::v4*>(olo + e) = l;
+  }
+}
+
+// The same tubelet rows, gathered from a table of already-resized u8 frames [Nt, S, S, 3] (stored byte order: channel c reads
+// byte c, no swap) through frame_idx [B, F] and normalised on the fly as (float(u) / 255 - mean[c]) / std[c] — true division, the
+// float32 arithmetic of the reference's ClipToTensor + Normalize — so the planes equal video_patchify_kernel's of those pixels bit
+// for bit.  4 pixels (along j) per thread: one 12-byte load (x % 4 == 0, S % 4 == 0: 4-byte aligned) holds all 3 channels.  A table
+// row outside [0, Nt) is never read: its pixels become NaN.
+template <typename T>
+__global__ void video_patchify_u8_kernel(const unsigned char* table, int Nt, int S, const int* frame_idx, int B, int F, int P, int ts,
+                                         float m0, float m1, float m2, float s0, float s1, float s2, T* ohi, T* olo) {
+  const int g = S / P, nt = F / ts, cols = 3 * ts * P * P;
+  const long long total4 = (long long)B * nt * g * g * cols / 4;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total4; i += (long long)gridDim.x * blockDim.x) {
+    const long long e = i * 4;
+    const int col = (int)(e % cols);
+    const long long row = e / cols;
+    const int c = col / (ts * P * P), dt = (col / (P * P)) % ts, ii = (col % (P * P)) / P, j = col % P;
+    const int pp = (int)(row % (g * g));
+    const long long bt = row / (g * g);
+    const int tt = (int)(bt % nt);
+    const long long b = bt / nt;
+    const int py = pp / g, pxx = pp % g;
+    const int n = frame_idx[b * F + tt * ts + dt];
+    const float m = c == 0 ? m0 : (c == 1 ? m1 : m2), s = c == 0 ? s0 : (c == 1 ? s1 : s2);
+    f32x4 v;
+    if ((unsigned)n < (unsigned)Nt) {
+      const unsigned* p = reinterpret_cast<const unsigned*>(table + (((long long)n * S + (py * P + ii)) * S + pxx * P + j) * 3);
+      const unsigned w0 = p[0], w1 = p[1], w2 = p[2];
+      const unsigned long long lo64 = (unsigned long long)w0 | ((unsigned long long)w1 << 32);
+      // bytes c, c + 3, c + 6, c + 9 of the 12
+      const unsigned b0 = (unsigned)(lo64 >> (8 * c)) & 255u, b1 = (unsigned)(lo64 >> (8 * (c + 3))) & 255u;
+      const unsigned b2 = c < 2 ? (unsigned)(lo64 >> ((8 * (c + 6)) & 63)) & 255u : (w2 & 255u);
+      const unsigned b3 = (w2 >> (8 * (c + 1))) & 255u;
+      v[0] = ((float)b0 / 255.0f - m) / s;
+      v[1] = ((float)b1 / 255.0f - m) / s;
+      v[2] = ((float)b2 / 255.0f - m) / s;
+      v[3] = ((float)b3 / 255.0f - m) / s;
+    } else {
+      v[0] = v[1] = v[2] = v[3] = __builtin_nanf("");
+    }
     typename T16<T>::v4 h, l;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -728,6 +780,24 @@ extern "C" int mer_video_patchify(const float* pixels, int B, int F, int C, int 
   else
     hipLaunchKernelGGL((video_patchify_kernel<bf16>), dim3(grid_for(n4, 256)), dim3(256), 0, st, pixels, B, F, C, H, W, P, ts, (bf16*)out_hi, (bf16*)out_lo);
   return check_launch("video_patchify");
+}
+
+extern "C" int mer_video_patchify_u8(const unsigned char* table, int n_table, int S, const int* frame_idx, int B, int F,
+                                     const float* mean3, const float* std3, int P, int ts, void* out_hi, void* out_lo, int dtype,
+                                     mer_stream_t stream) {
+  using namespace mer;
+  MER_REQUIRE(table && frame_idx && mean3 && std3 && out_hi && B > 0 && n_table > 0, MER_EINVAL, "mer_video_patchify_u8: bad args");
+  MER_REQUIRE(P > 0 && ts > 0 && S % P == 0 && P % 4 == 0 && F % ts == 0 && ((uintptr_t)table & 3) == 0, MER_ESHAPE,
+              "mer_video_patchify_u8: S=%d P=%d F=%d ts=%d unsupported (S %% P == 0, P %% 4 == 0, F %% ts == 0, 4-byte aligned table)", S, P, F, ts);
+  const long long n4 = (long long)B * F * 3 * S * S / 4;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == MER_DT_F16)
+    hipLaunchKernelGGL((video_patchify_u8_kernel<f16>), dim3(grid_for(n4, 256)), dim3(256), 0, st, table, n_table, S, frame_idx, B, F, P, ts,
+                       mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], (f16*)out_hi, (f16*)out_lo);
+  else
+    hipLaunchKernelGGL((video_patchify_u8_kernel<bf16>), dim3(grid_for(n4, 256)), dim3(256), 0, st, table, n_table, S, frame_idx, B, F, P, ts,
+                       mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], (bf16*)out_hi, (bf16*)out_lo);
+  return check_launch("video_patchify_u8");
 }
 
 extern "C" int mer_add_pos(float* x, const float* pos, long long rows, int P, int D, mer_stream_t stream) {

@@ -1237,6 +1237,163 @@ class HipVideoMAEModel(_HipModule):
         return self.forward_raw(pixel_values, hidden=False, seg_start=starts, seg_len=[per] * len(starts))[1]
 
 
+class HipVideoMAEFinetuneModel(HipVideoMAEModel):
+    """MER2024's fine-tuned VideoMAE (feature_extraction/visual/extract_sun_videomae.py: the vendored videomae/modeling_finetune.py
+    `VisionTransformer`, joint attention, use_mean_pooling=False): the feature is norm(x).mean(1) over all tokens.  The training
+    checkpoint is re-keyed into the HF-VideoMAE layout HipVideoMAEModel consumes, so presets, plane sharing and the load-time self-check
+    are those of the other encoders.  `forward_frames` runs views straight from a device table of resized u8 frames
+    (mer_videomae_forward_frames); `__call__` takes float pixels in the reference's (B, C, T, H, W) layout."""
+
+    # model name -> (input size, patch size) of the script's command lines (extract_sun_videomae.py:367-390); D / depth / MLP come from the weights
+    MODELS = {"vit_base_patch16_160": (160, 16), "vit_base_patch16_224": (224, 16), "vit_large_patch16_224": (224, 16)}
+    MEAN, STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)   # ImageNet, applied to the BGR bytes as stored (kinetics.py:43-47)
+    NUM_FRAMES, TUBELET = 16, 2
+
+    @staticmethod
+    def load_checkpoint(path, model_key="model|module"):
+        """torch.load of a training checkpoint -> its state dict (extract_sun_videomae.py:297-307).  Training checkpoints carry the run's
+        argparse.Namespace under 'args': that one class is allow-listed for weights_only loading; anything else unpickleable raises."""
+        import argparse
+        with torch.serialization.safe_globals([argparse.Namespace]):
+            ck = torch.load(path, map_location="cpu", weights_only=True)
+        for k in model_key.split("|"):
+            if k in ck:
+                return ck[k]
+        return ck
+
+    @classmethod
+    def remap_state_dict(cls, sd):
+        """Reference checkpoint keys -> (HF-VideoMAE state dict, unused keys).  `backbone.` / `encoder.` prefixes are stripped
+        (:309-318); qkv rows split into query / key / value, q_bias / v_bias the query / value biases (key bias 0); layer scale
+        gamma_1 / gamma_2 folded into attn.proj / mlp.fc2; a missing `norm.*` is the identity affine the non-strict load leaves."""
+        src = {}
+        for k, v in sd.items():
+            k2 = k[9:] if k.startswith("backbone.") else (k[8:] if k.startswith("encoder.") else k)
+            src[k2] = v.float() if torch.is_tensor(v) and v.is_floating_point() else v
+        used = set()
+
+        def take(k):
+            used.add(k)
+            return src[k]
+        if "patch_embed.proj.weight" not in src:
+            raise _lib.MerError("VideoMAE checkpoint: no patch_embed.proj.weight (after stripping backbone. / encoder.)")
+        out = {"embeddings.patch_embeddings.projection.weight": take("patch_embed.proj.weight"),
+               "embeddings.patch_embeddings.projection.bias": take("patch_embed.proj.bias")}
+        D = out["embeddings.patch_embeddings.projection.weight"].shape[0]
+        depth = 0
+        while f"blocks.{depth}.attn.qkv.weight" in src:
+            depth += 1
+        for k in src:
+            if k.startswith("blocks.") and k.split(".")[1].isdigit() and int(k.split(".")[1]) < depth:
+                part = k.split(".")[2]
+                if part not in ("norm1", "norm2", "attn", "mlp", "gamma_1", "gamma_2") or (part == "attn" and k.split(".")[3] not in ("qkv", "q_bias", "v_bias", "proj")):
+                    raise _lib.MerError(f"VideoMAE checkpoint key {k!r}: only attn_type='joint' blocks are supported")
+            elif k.startswith("blocks."):
+                raise _lib.MerError(f"VideoMAE checkpoint key {k!r}: only attn_type='joint' blocks are supported")
+        if depth == 0:
+            raise _lib.MerError("VideoMAE checkpoint: no blocks.N.attn.qkv.weight")
+        zeros = torch.zeros(D)
+        for l in range(depth):
+            b, q = f"blocks.{l}.", f"encoder.layer.{l}."
+            a = q + "attention.attention."
+            wq, wk, wv = take(b + "attn.qkv.weight").chunk(3, 0)
+            out[a + "query.weight"], out[a + "key.weight"], out[a + "value.weight"] = wq.contiguous(), wk.contiguous(), wv.contiguous()
+            out[a + "query.bias"] = take(b + "attn.q_bias") if b + "attn.q_bias" in src else zeros
+            out[a + "key.bias"] = zeros
+            out[a + "value.bias"] = take(b + "attn.v_bias") if b + "attn.v_bias" in src else zeros
+            wo, bo = take(b + "attn.proj.weight"), take(b + "attn.proj.bias")
+            w2, b2 = take(b + "mlp.fc2.weight"), take(b + "mlp.fc2.bias")
+            if b + "gamma_1" in src:
+                g1 = take(b + "gamma_1")
+                wo, bo = g1[:, None] * wo, g1 * bo
+            if b + "gamma_2" in src:
+                g2 = take(b + "gamma_2")
+                w2, b2 = g2[:, None] * w2, g2 * b2
+            out[q + "attention.output.dense.weight"], out[q + "attention.output.dense.bias"] = wo, bo
+            out[q + "layernorm_before.weight"], out[q + "layernorm_before.bias"] = take(b + "norm1.weight"), take(b + "norm1.bias")
+            out[q + "layernorm_after.weight"], out[q + "layernorm_after.bias"] = take(b + "norm2.weight"), take(b + "norm2.bias")
+            out[q + "intermediate.dense.weight"], out[q + "intermediate.dense.bias"] = take(b + "mlp.fc1.weight"), take(b + "mlp.fc1.bias")
+            out[q + "output.dense.weight"], out[q + "output.dense.bias"] = w2, b2
+        if "norm.weight" in src:
+            out["layernorm.weight"], out["layernorm.bias"] = take("norm.weight"), take("norm.bias")
+        else:   # the module's own init (ones / zeros) survives the non-strict load
+            out["layernorm.weight"], out["layernorm.bias"] = torch.ones(D), torch.zeros(D)
+        unused = sorted(k for k in src if k not in used and k != "pos_embed")
+        return out, unused
+
+    @classmethod
+    def config_for(cls, hf_sd, model="vit_base_patch16_160", img_size=None, patch_size=None):
+        """transformers.VideoMAEConfig of a re-keyed state dict: S / P from the model name (or the overrides), D / depth / MLP width from
+        the weights, heads = D / 64, 16 frames, tubelet 2, exact GELU, LayerNorm eps 1e-6."""
+        from transformers import VideoMAEConfig
+        if model not in cls.MODELS and (img_size is None or patch_size is None):
+            raise _lib.MerError(f"unknown VideoMAE model {model!r}: one of {sorted(cls.MODELS)} (or pass img_size and patch_size)")
+        S, P = cls.MODELS.get(model, (None, None))
+        S, P = img_size or S, patch_size or P
+        w = hf_sd["embeddings.patch_embeddings.projection.weight"]
+        D = w.shape[0]
+        if w.dim() != 5 or tuple(w.shape[1:]) != (3, cls.TUBELET, P, P):
+            raise _lib.MerError(f"patch_embed.proj.weight {tuple(w.shape)} does not fit {model} (3 x {cls.TUBELET} x {P} x {P})")
+        if D % 64:
+            raise _lib.MerError(f"VideoMAE width {D} is not a multiple of the head size 64")
+        depth = sum(1 for k in hf_sd if k.endswith("attention.attention.query.weight"))
+        mlp = hf_sd["encoder.layer.0.intermediate.dense.weight"].shape[0]
+        return VideoMAEConfig(image_size=S, patch_size=P, num_channels=3, num_frames=cls.NUM_FRAMES, tubelet_size=cls.TUBELET, hidden_size=D,
+                              num_hidden_layers=depth, num_attention_heads=D // 64, intermediate_size=mlp, hidden_act="gelu",
+                              layer_norm_eps=1e-6, qkv_bias=True, use_mean_pooling=False)
+
+    @classmethod
+    def from_state_dict(cls, sd, model="vit_base_patch16_160", img_size=None, patch_size=None, attn_type="joint", use_mean_pooling=False,
+                        keep_temporal_dim=False, **kw):
+        """A reference state dict (any of the checkpoint's prefixes) -> model.  Unused keys (head.*, decoder.*, fc_norm.*, ...) are
+        reported as a warning, as the reference's non-strict load prints them.  Only the script's architecture is covered: joint
+        attention, use_mean_pooling=False, no keep_temporal_dim."""
+        import warnings
+        if attn_type != "joint" or use_mean_pooling or keep_temporal_dim:
+            raise _lib.MerError(f"{cls.__name__}: attn_type={attn_type!r}, use_mean_pooling={use_mean_pooling}, keep_temporal_dim={keep_temporal_dim} "
+                                "are not supported (extract_sun_videomae.py runs joint attention, use_mean_pooling=False, keep_temporal_dim=False)")
+        hf_sd, unused = cls.remap_state_dict(sd)
+        if unused:
+            warnings.warn(f"{cls.__name__}: weights not used by the feature path: {unused}")
+        m = cls(hf_sd, cls.config_for(hf_sd, model, img_size, patch_size), **kw)
+        m.model_name, m.unused_keys = model, unused
+        return m
+
+    @classmethod
+    def from_checkpoint(cls, path, model="vit_base_patch16_160", device="cuda:0", precision="mean", self_check=True, model_key="model|module", **kw):
+        return cls.from_state_dict(cls.load_checkpoint(path, model_key), model=model, device=device, precision=precision, self_check=self_check,
+                                   **kw)
+
+    @property
+    def image_size(self):
+        return self._cfg.image_size
+
+    def forward_frames(self, table, frame_idx, hidden=False):
+        """Views straight from resized u8 frames: table device uint8 [Nt, S, S, 3] (stored byte order), frame_idx device int32 [B, 16]
+        table rows -> (last_hidden_state [B, tokens, D] or None, features [B, D] = norm(x).mean(1) per view)."""
+        c = self._cfg
+        assert table.is_cuda and table.dtype == torch.uint8 and table.is_contiguous() and tuple(table.shape[1:]) == (c.image_size, c.image_size, 3), table.shape
+        assert frame_idx.is_cuda and frame_idx.dtype == torch.int32 and frame_idx.is_contiguous() and frame_idx.dim() == 2 and frame_idx.shape[1] == c.num_frames
+        return self._forward_frames(table, frame_idx, hidden)
+
+    def _forward_frames(self, table, frame_idx, hidden):
+        with torch.cuda.device(self.device):
+            B, D = frame_idx.shape[0], self.config.hidden_size
+            out = torch.empty((B, self.num_patches, D), dtype=torch.float32, device=self.device) if hidden else None
+            ss, sl, nseg = self._seg([b * self.num_patches for b in range(B)], [self.num_patches] * B)
+            pooled = torch.empty((nseg, D), dtype=torch.float32, device=self.device)
+            wp, wn = self._workspace(_lib.lib().mer_videomae_workspace_bytes(self._handle, B))
+            mean3, std3 = (C.c_float * 3)(*self.MEAN), (C.c_float * 3)(*self.STD)
+            _lib.check(_lib.lib().mer_videomae_forward_frames(
+                self._handle, table.data_ptr(), table.shape[0], frame_idx.data_ptr(), B, C.addressof(mean3), C.addressof(std3), wp, wn,
+                out.data_ptr() if hidden else None, ss.data_ptr(), sl.data_ptr(), nseg, pooled.data_ptr(), stream()), "mer_videomae_forward_frames")
+            return out, pooled
+
+    def __call__(self, videos=None, **_):
+        """model(videos, save_feature=True)[1] of engine_for_finetuning.py:22: float pixels [B, C, T, H, W] -> features [B, D]."""
+        return self.extract_utterance(videos.permute(0, 2, 1, 3, 4))
+
+
 # =================================================================================================
 class HipBertModel(_HipModule):
     """BERT / RoBERTa family (post-LN encoder-only text models): BERT, RoBERTa, MacBERT / PERT / LERT / Chinese-RoBERTa-wwm

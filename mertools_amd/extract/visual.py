@@ -392,3 +392,132 @@ def extract_by_name(model_name, face_dir, save_dir, feature_level='UTTERANCE', g
     loads the checkpoint by name and runs its branch; `kw` goes to that branch's driver (vids, workers, device_preprocess ...)."""
     model, driver = load_model(model_name, gpu, precision)
     return globals()[driver](model, face_dir, save_dir, feature_level, **kw)
+
+
+# ---- MER2024's fine-tuned VideoMAE (feature_extraction/visual/extract_sun_videomae.py) ----------------------------------------
+# name (FEATURE_DIR_OF stem or IMAGE_RANK_LOW2HIGH entry) -> (checkpoint under PATH_TO_PRETRAINED_MODELS, model name) (MER2024 README:49-50)
+SUN_VIDEOMAE = {'videomae-base-VoxCeleb2-99': ('videomae-base-VoxCeleb2/checkpoint-99.pth', 'vit_base_patch16_160'),
+                'videomae-base-K400-mer2023-299': ('videomae-base-K400-mer2023/checkpoint-299.pth', 'vit_base_patch16_224')}
+SUN_VIDEOMAE['VideoMAE-base (VoxCeleb2)'] = SUN_VIDEOMAE['videomae-base-VoxCeleb2-99']
+SUN_VIDEOMAE['VideoMAE-base (MER2023)'] = SUN_VIDEOMAE['videomae-base-K400-mer2023-299']
+
+
+def sun_videomae_save_dir(feature_root, checkpoint, feature_level):
+    """PATH_TO_FEATURES/{checkpoint parent dir}-{epoch}-{UTT|FRA} (extract_sun_videomae.py:232-235)."""
+    from .sun_videomae import save_dir_name
+    return os.path.join(feature_root, save_dir_name(checkpoint, feature_level))
+
+
+def _read_face_npy(path):
+    frames = np.load(path)
+    if frames.dtype != np.uint8 or frames.ndim != 4 or frames.shape[-1] != 3:
+        raise ValueError(f"{path}: expected uint8 frames [N, H, W, 3], got {frames.dtype} {frames.shape}")
+    if frames.shape[0] == 0:
+        raise ValueError(f"{path}: the video has no frames")
+    return np.ascontiguousarray(frames)
+
+
+def extract_sun_videomae(model, face_dir, save_dir, feature_level='UTTERANCE', *, vids=None, rank=None, world=None, windows_per_batch=32,
+                         dedup=True, skip_existing=True, workers=0, async_save=True, videos_per_group=16):
+    """The loop of extract_sun_videomae.py:329-355 on the HIP encoder (`model`: HipVideoMAEFinetuneModel).  Inputs are
+    glob(face_dir/*/*.npy), vid = the file's basename; an existing output is skipped.  Per group of videos: the u8 frames go up
+    through pinned memory, each video's frames are resized ONCE (Pillow-exact bilinear to S x S) into one device table, the views of
+    every video of the group run in batches of `windows_per_batch` straight from that table (mer_videomae_forward_frames), and each
+    video's float64 array is rebuilt on the host as final_test builds it.  dedup=True forwards each distinct window once
+    (extract/sun_videomae.py says why that is exact); dedup=False forwards all 4 views of every item, as the reference does."""
+    import glob
+    from concurrent.futures import ThreadPoolExecutor
+    from ..distributed import my_share
+    from .pipeline import writer
+    from .resize import resize_crop_u8
+    from .sun_videomae import plan_views, reduce_items, reduce_views
+    if feature_level not in ('UTTERANCE', 'FRAME'):
+        raise ValueError(f"feature_level must be UTTERANCE or FRAME, not {feature_level!r}")
+    os.makedirs(save_dir, exist_ok=True)
+    files = sorted(glob.glob(os.path.join(face_dir, '*', '*.npy')))
+    if vids is not None:
+        keep = set(vids)
+        files = [f for f in files if os.path.basename(f).rsplit('.', 1)[0] in keep]
+    files = my_share(files, rank, world)
+    todo = []
+    for f in files:
+        vid = os.path.basename(f).rsplit('.', 1)[0]
+        out = os.path.join(save_dir, f'{vid}.npy')
+        if not (skip_existing and os.path.exists(out)):
+            todo.append((f, out))
+    dev, S, F = model.device, model.image_size, model._cfg.num_frames
+    groups = [todo[i:i + videos_per_group] for i in range(0, len(todo), videos_per_group)]
+    pool = ThreadPoolExecutor(workers) if workers > 0 else None
+
+    def read(g):
+        return [_read_face_npy(f) for f, _ in g]
+
+    def reads():   # `workers` groups read ahead on threads, no more
+        if pool is None:
+            yield from (read(g) for g in groups)
+            return
+        ahead = [pool.submit(read, g) for g in groups[:workers]]
+        for i in range(len(groups)):
+            got = ahead.pop(0).result()
+            if i + workers < len(groups):
+                ahead.append(pool.submit(read, groups[i + workers]))
+            yield got
+    try:
+        with torch.cuda.device(dev), writer(dev, async_save) as w:
+            for group, frames in zip(groups, reads()):
+                with span("sun_videomae.table"):
+                    pieces, base = [], []
+                    for fr in frames:
+                        d = torch.from_numpy(fr).pin_memory().to(dev, non_blocking=True)
+                        if d.shape[1:3] != (S, S):
+                            d = resize_crop_u8(d, S, filt='bilinear', exact=True)
+                        base.append(sum(p.shape[0] for p in pieces))
+                        pieces.append(d)
+                    table = torch.cat(pieces, 0) if len(pieces) > 1 else pieces[0]
+                plans, rows, spans = [], [], []
+                for fr, b in zip(frames, base):
+                    plan = plan_views(len(fr), feature_level)
+                    win = plan.windows if dedup else plan.windows[plan.item_window]
+                    spans.append((len(rows), len(win)))
+                    rows.extend((win + b).tolist())
+                    plans.append(plan)
+                idx = torch.tensor(rows, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+                feats = torch.empty((len(rows), model.config.hidden_size), dtype=torch.float32, device=dev)
+                with span("sun_videomae.forward"):
+                    for s in range(0, len(rows), windows_per_batch):
+                        feats[s:s + windows_per_batch] = model._forward_frames(table, idx[s:s + windows_per_batch], False)[1]
+
+                def save(arr, group=group, plans=plans, spans=spans):
+                    for (_, out), plan, (s0, n) in zip(group, plans, spans):
+                        per = arr[s0:s0 + n]
+                        emb = reduce_views(per, plan) if dedup else reduce_items(per, plan.item_frmid, feature_level)
+                        npy_save(out, emb)
+                w.submit(feats, save)
+    finally:
+        if pool:
+            pool.shutdown()
+    return [out for _, out in todo]
+
+
+def extract_sun_videomae_by_name(name_or_path, face_dir, feature_root, feature_level='UTTERANCE', gpu=0, precision="mean", model=None,
+                                 **kw):
+    """`python extract_sun_videomae.py --finetune <ckpt> --model <model> --feature_level L` for one face directory.  `name_or_path`: one
+    of the two MER2024 checkpoints by feature-directory stem ('videomae-base-VoxCeleb2-99', 'videomae-base-K400-mer2023-299') or ranking
+    name, found under PATH_TO_PRETRAINED_MODELS, or a checkpoint path (then `model` names the architecture when its parent directory is
+    not one of the two).  Writes to sun_videomae_save_dir(feature_root, ...) and returns that directory."""
+    from .. import config
+    from ..encoders import HipVideoMAEFinetuneModel
+    if name_or_path in SUN_VIDEOMAE:
+        rel, arch = SUN_VIDEOMAE[name_or_path]
+        ckpt = os.path.join(config.PATH_TO_PRETRAINED_MODELS, rel)
+    else:
+        ckpt = name_or_path
+        known = {os.path.dirname(r): a for r, a in SUN_VIDEOMAE.values()}
+        arch = model or known.get(os.path.basename(os.path.dirname(os.path.abspath(ckpt))))
+        if arch is None:
+            raise ValueError(f"{ckpt}: pass model= (one of {sorted(HipVideoMAEFinetuneModel.MODELS)})")
+    torch.cuda.set_device(max(gpu, 0))
+    m = HipVideoMAEFinetuneModel.from_checkpoint(ckpt, model=model or arch, device=f'cuda:{max(gpu, 0)}', precision=precision)
+    save_dir = sun_videomae_save_dir(feature_root, ckpt, feature_level)
+    extract_sun_videomae(m, face_dir, save_dir, feature_level, **kw)
+    return save_dir

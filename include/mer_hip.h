@@ -354,8 +354,45 @@ int mer_fusion_group_step(const mer_fusion_group* desc, int train, mer_stream_t 
 int mer_fusion_group_dropout_mask(uint64_t seed, int step, int site, int rows, int cols, float p, uint8_t* keep,
                                   mer_stream_t stream);
 
+/* ---- grouped Attention_TOPN training (csrc/fusion_topn_group.hip): the same contract as mer_fusion_group for G independent
+ *      Attention_TOPN models (MER2024/toolkit/models/attention_topn.py, feat_type utt) of M feature streams (1..18) with an
+ *      emotion head of C1 classes and a valence head of C2 in {0, 1} outputs — the MER2024 / MER2025 / MER2026 multi-feature
+ *      recipe.  The launch count of a step depends on neither G nor M.  Each [G, P] row is in model.parameters() order:
+ *      encoder0 .. encoder{M-1} (linear_{1,2,3}.{weight, bias}), attention_mlp (input width M * H), fc_att (M outputs),
+ *      fc_out_1, fc_out_2 (empty when C2 = 0).  With C2 = 0 the loss is CE alone; val and out_val may be NULL.  For M = 3,
+ *      C2 = 1 and dropout 0 the results are bitwise mer_fusion_group_step's.  The dropout counter has its own layout
+ *      (site i < M: input of encoder i, site M: input of attention_mlp), documented in csrc/fusion_topn_group.hip. */
+#define MER_TOPN_MAX_STREAMS 18
+typedef struct {
+  int G, B, n_steps;                 /* models, rows per minibatch (<= 2048), steps in the index / count / out_* tables */
+  int M, H, C1, C2;                  /* streams (1..18), hidden dim (M * H < 65536), emotion classes (1..64), valence outputs (0 | 1) */
+  int D[MER_TOPN_MAX_STREAMS];       /* stream widths (0 < D < 65536), the first M are read */
+  long long P;                       /* parameters per model */
+  float* params; float* grads; float* adam_m; float* adam_v;   /* [G, P] */
+  int* step;                         /* [G] optimiser steps taken (Adam bias correction uses step + 1) */
+  const float* lr; const float* weight_decay; const float* grad_clip; const float* dropout;   /* [G]; grad_clip <= 0: none */
+  const uint64_t* seed;              /* [G] dropout seeds (may be NULL: 0) */
+  float beta1, beta2, eps;
+  const float* feat[MER_TOPN_MAX_STREAMS];   /* device split tables [n_rows, D[i]], the first M are read */
+  const int* emo; const float* val;  /* [n_rows] class index, valence (val may be NULL when C2 = 0) */
+  long long n_rows;
+  const int* index;                  /* [n_steps, G, B] table rows */
+  const int* count;                  /* [n_steps, G] rows used (<= B) */
+  int* cursor;                       /* current step, advanced by each step (may be NULL) */
+  float* out_loss; float* out_emo; float* out_val;   /* [n_steps, G], [n_steps, G, B, C1], [n_steps, G, B]; each may be NULL */
+  void* workspace; long long workspace_bytes;        /* mer_fusion_topn_group_workspace_bytes(desc) */
+} mer_fusion_topn_group;
+/* Negative status (and mer_last_error() naming the function) for M outside 1..18, a width <= 0 or >= 65536, M * H >= 65536,
+ * C1 outside 1..64, C2 outside {0, 1}, B <= 0 or > 2048; none of these checks touches a GPU. */
+long long mer_fusion_topn_group_param_count(int M, const int* D, int H, int C1, int C2);
+long long mer_fusion_topn_group_workspace_bytes(const mer_fusion_topn_group* desc);
+int mer_fusion_topn_group_step(const mer_fusion_topn_group* desc, int train, mer_stream_t stream);
+/* keep[r, c] (uint8 [rows, cols], rows <= 2048) of the dropout mask the step uses at (seed, step, site), site 0..18. */
+int mer_fusion_topn_group_dropout_mask(uint64_t seed, int step, int site, int rows, int cols, float p, uint8_t* keep,
+                                       mer_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------ */
-/* Encoder level                                                                               */
+/* Encoder level                                                                              */
 /* ------------------------------------------------------------------------------------------ */
 
 typedef struct { const void* hi; const void* lo; const void* mx;   /* 16-bit weight planes [N,K] (+ MX residual plane for passes == 4, may be null) */

@@ -129,6 +129,25 @@ class FusionGroup(C.Structure):
                 ("workspace", c_void_p), ("workspace_bytes", c_ll)]
 
 
+class FusionTopnGroup(C.Structure):
+    """mer_fusion_topn_group (include/mer_hip.h): mer_fusion_group with M streams (widths D[18], tables feat[18]) and C2 in {0, 1}."""
+    _fields_ = [("G", c_int), ("B", c_int), ("n_steps", c_int),
+                ("M", c_int), ("H", c_int), ("C1", c_int), ("C2", c_int),
+                ("D", c_int * 18),
+                ("P", c_ll),
+                ("params", c_void_p), ("grads", c_void_p), ("adam_m", c_void_p), ("adam_v", c_void_p),
+                ("step", c_void_p),
+                ("lr", c_void_p), ("weight_decay", c_void_p), ("grad_clip", c_void_p), ("dropout", c_void_p),
+                ("seed", c_void_p),
+                ("beta1", c_float), ("beta2", c_float), ("eps", c_float),
+                ("feat", c_void_p * 18),
+                ("emo", c_void_p), ("val", c_void_p),
+                ("n_rows", c_ll),
+                ("index", c_void_p), ("count", c_void_p), ("cursor", c_void_p),
+                ("out_loss", c_void_p), ("out_emo", c_void_p), ("out_val", c_void_p),
+                ("workspace", c_void_p), ("workspace_bytes", c_ll)]
+
+
 # name -> (restype, argtypes); every symbol include/mer_hip.h declares must appear here.
 _PROTOS = {
     "mer_version": (C.c_char_p, []),
@@ -190,6 +209,10 @@ _PROTOS = {
     "mer_fusion_group_workspace_bytes": (c_ll, [C.POINTER(FusionGroup)]),
     "mer_fusion_group_step": (c_int, [C.POINTER(FusionGroup), c_int, c_void_p]),
     "mer_fusion_group_dropout_mask": (c_int, [C.c_uint64, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
+    "mer_fusion_topn_group_param_count": (c_ll, [c_int, C.POINTER(c_int), c_int, c_int, c_int]),
+    "mer_fusion_topn_group_workspace_bytes": (c_ll, [C.POINTER(FusionTopnGroup)]),
+    "mer_fusion_topn_group_step": (c_int, [C.POINTER(FusionTopnGroup), c_int, c_void_p]),
+    "mer_fusion_topn_group_dropout_mask": (c_int, [C.c_uint64, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     "mer_hubert_create": (c_int, [C.POINTER(HubertConfig), C.POINTER(HubertWeights), C.POINTER(c_void_p)]),
     "mer_hubert_destroy": (None, [c_void_p]),
     "mer_hubert_out_frames": (c_int, [c_void_p, c_int]),

@@ -3,8 +3,10 @@ authors' cluster paths; here every dataset root hangs off MER_DATA_ROOT (default
 re-pointed at run time with set_data_root()."""
 import os
 
-_DATASETS = {'MER2023': 'mer2023-dataset-process', 'MER2024': 'mer2024-dataset-process'}
-_LABELS = {'MER2023': 'label-6way.npz', 'MER2024': 'label-6way.npz'}
+_DATASETS = {'MER2023': 'mer2023-dataset-process', 'MER2024': 'mer2024-dataset-process', 'MER2025': 'mer2025-dataset-process',
+             'MER2026': 'mer2026-dataset-process'}
+_LABELS = {'MER2023': 'label-6way.npz', 'MER2024': 'label-6way.npz', 'MER2025': 'track1_label_6way.npz',
+           'MER2026': 'track1_label_6way.npz'}
 
 DATA_DIR, PATH_TO_RAW_AUDIO, PATH_TO_RAW_VIDEO, PATH_TO_RAW_FACE = {}, {}, {}, {}
 PATH_TO_TRANSCRIPTIONS, PATH_TO_FEATURES, PATH_TO_LABEL = {}, {}, {}

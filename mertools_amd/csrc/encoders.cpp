@@ -874,6 +874,7 @@ extern "C" int mer_abi_sizeof(const char* name) {
   MER_SZ(mer_videomae_config);
   MER_SZ(mer_videomae_weights);
   MER_SZ(mer_fusion_group);
+  MER_SZ(mer_fusion_topn_group);
 #undef MER_SZ
   return MER_EINVAL;
 }

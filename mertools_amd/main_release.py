@@ -153,7 +153,8 @@ def build_parser():
                    help="the reference's loop verbatim (one kernel launch per op, 3-5 host syncs per minibatch) instead of one captured "
                         "HIP graph per minibatch with per-epoch result copies; same results, for bit-comparison")
     p.add_argument('--parallel_folds', action='store_true', default=False,
-                   help="train the 5 folds of the run as ONE group (mer_fusion_group_step: --model attention --feat_type utt, MER2023 "
+                   help="train the 5 folds of the run as ONE group (mer_fusion_group_step: --model attention --feat_type utt, MER2023; "
+                        "mer_fusion_topn_group_step: --model attention_topn --feat_type utt --fusion_topn n, MER2024 / MER2025 / MER2026 "
                         "only); same CPU-generator draws as the sequential loop, so at dropout 0 the same results and file names. "
                         "Dropout masks come from an in-kernel hash seeded by (effective seed, fold): a different draw from the "
                         "sequential path's. Without --seed the effective seed is drawn from python's random and printed")
@@ -286,36 +287,48 @@ def _save_results(args, folder_save, folder_duration, dataloader_class, n_tests,
         _, test_result = dataloader_class.calculate_results(emo_probs, emo_labels, val_preds, val_labels)
         save_path = f'{save_resroot}/test{jj + 1}_{prefix_name}_{test_result}_{name_time}.npz'
         print(f'save results in {save_path}')
-        if args.dataset == 'MER2024':   # MER2024/main-release.py:288-290 also stores the fold-averaged test probabilities
+        # MER2024/main-release.py:288-290 (MER2026/MER2026_Track1/main-release.py:280-288) also store the fold-averaged test probabilities
+        if args.dataset in TOPN_DATASETS:
             np.savez_compressed(save_path, emo_probs=emo_probs, args=np.array(args, dtype=object))
         else:
             np.savez_compressed(save_path, args=np.array(args, dtype=object))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# --parallel_folds / --num_trials: every fold (and trial) of the run in one group (fusion_group.FusionGroupTrainer)
+# --parallel_folds / --num_trials: every fold (and trial) of the run in one group (fusion_group.FusionGroupTrainer for
+# Attention on MER2023, fusion_topn_group.FusionTopnGroupTrainer for Attention_TOPN on MER2024 / MER2025 / MER2026)
 # ---------------------------------------------------------------------------------------------------------------------
 GROUP_SCOPE = "--model attention --feat_type utt --dataset MER2023 (emotion + valence heads)"
+GROUP_SCOPE_TOPN = "--model attention_topn --feat_type utt --dataset MER2024|MER2025|MER2026 --fusion_topn n"
+TOPN_DATASETS = ('MER2024', 'MER2025', 'MER2026')
 
 
 def check_group_scope(args):
-    """Raises ValueError unless the run is one the grouped kernels build (checked before anything touches the GPU)."""
+    """Raises ValueError unless the run is one the grouped kernels build (checked before anything touches the GPU); returns the
+    model the group trains: 'attention' or 'attention_topn'."""
     if args.num_trials is not None:
         if args.seed is None:
             raise ValueError("--num_trials needs --seed s (trial t runs with the effective seed s + t)")
         if args.num_trials < 1:
             raise ValueError("--num_trials must be >= 1")
     bad = []
-    if args.model != 'attention':
+    topn = args.model == 'attention_topn'
+    if args.model not in ('attention', 'attention_topn'):
         bad.append(f'--model {args.model}')
     if args.feat_type != 'utt':
         bad.append(f'--feat_type {args.feat_type}')
-    if args.dataset != 'MER2023' or args.train_dataset is not None or args.test_dataset is not None:
-        bad.append(f'--dataset {args.dataset}')
-    if args.test_snr is not None or args.train_snr is not None or args.fusion_topn is not None or args.eager:
-        bad.append('--train_snr / --test_snr / --fusion_topn / --eager')
+    if (args.dataset not in (TOPN_DATASETS if topn else ('MER2023',)) or args.train_dataset is not None
+            or args.test_dataset is not None):
+        bad.append(f'--model {args.model} --dataset {args.dataset}')
+    if topn and args.fusion_topn is None:
+        bad.append('--model attention_topn without --fusion_topn')
+    if not topn and args.fusion_topn is not None:
+        bad.append(f'--model {args.model} --fusion_topn')
+    if args.test_snr is not None or args.train_snr is not None or args.eager:
+        bad.append('--train_snr / --test_snr / --eager')
     if bad:
-        raise ValueError(f"--parallel_folds / --num_trials support {GROUP_SCOPE} only, not {', '.join(bad)}")
+        raise ValueError(f"--parallel_folds / --num_trials support {GROUP_SCOPE} or {GROUP_SCOPE_TOPN} only, not {', '.join(bad)}")
+    return args.model
 
 
 def _base_seed_draw():
@@ -352,8 +365,12 @@ def _batches(order, B):
 def main_group(args):
     """--parallel_folds [--num_trials N]: returns the folder_save list of the run (a list of them, one per trial, with --num_trials)."""
     import copy
-    from .fusion_group import FusionGroupTrainer, dropout_seed
-    check_group_scope(args)
+    from .fusion_group import dropout_seed
+    topn = check_group_scope(args) == 'attention_topn'
+    if topn:
+        from .fusion_topn_group import FusionTopnGroupTrainer as Trainer
+    else:
+        from .fusion_group import FusionGroupTrainer as Trainer
     torch.cuda.set_device(args.gpu)
     if args.data_root:
         config.set_data_root(args.data_root)
@@ -379,8 +396,8 @@ def main_group(args):
             folds = mer.random_split_indexes(len(data['sets'][0]), mer.num_folder)
             a.output_dim1, a.output_dim2, a.metric_name = mer.args.output_dim1, mer.args.output_dim2, mer.args.metric_name
         a.audio_dim, a.text_dim, a.video_dim = data['sets'][0].get_featdim()
-        if a.output_dim1 == 0 or a.output_dim2 != 1:
-            raise ValueError(f"--parallel_folds supports {GROUP_SCOPE} only")
+        if a.output_dim1 == 0 or a.output_dim2 not in ((0, 1) if topn else (1,)):
+            raise ValueError(f"--parallel_folds supports {GROUP_SCOPE} or {GROUP_SCOPE_TOPN} only")
         models, orders = fold_plan(a, folds, data['n_tests'], a.epochs)
         trials.append(dict(args=a, seed=a.seed, models=models, orders=orders, save_resroot=save_resroot, prefix_name=prefix_name))
 
@@ -390,18 +407,27 @@ def main_group(args):
     names = sum((c[3] for c in cols), [])
     emo_all = torch.cat([c[1] for c in cols]).numpy()
     val_all = torch.cat([c[2] for c in cols]).numpy()
-    tables = [torch.cat([c[0][k] for c in cols]) for k in ('audios', 'texts', 'videos')]
+    if topn:   # Data_Feat_TOPN.collater: feat0 .. feat{M-1}
+        tables = [torch.cat([c[0][f'feat{i}'] for c in cols]) for i in range(len(cols[0][0]))]
+    else:
+        tables = [torch.cat([c[0][k] for c in cols]) for k in ('audios', 'texts', 'videos')]
+
+    def upload(trainer):
+        if topn:
+            trainer.set_tables(tables, emo_all, val_all if trainer.C2 else None)
+        else:
+            trainer.set_tables(*tables, emo_all, val_all)
 
     by_h = {}
     for t, tr in enumerate(trials):
         by_h.setdefault(tr['args'].hidden_dim, []).append(t)
     for h, members in by_h.items():
-        _train_group([trials[t] for t in members], data, tables, emo_all, val_all, names, offs, FusionGroupTrainer, dropout_seed)
+        _train_group([trials[t] for t in members], data, upload, emo_all, val_all, names, offs, Trainer, dropout_seed)
     outs = [tr['folder_save'] for tr in trials]
     return outs if args.num_trials is not None else outs[0]
 
 
-def _train_group(trials, data, tables, emo_all, val_all, names, offs, FusionGroupTrainer, dropout_seed):
+def _train_group(trials, data, upload, emo_all, val_all, names, offs, Trainer, dropout_seed):
     dataloader_class, n_tests = data['cls'], data['n_tests']
     a0 = trials[0]['args']
     B, epochs = a0.batch_size, a0.epochs
@@ -410,10 +436,10 @@ def _train_group(trials, data, tables, emo_all, val_all, names, offs, FusionGrou
     print(f'====== Training and Evaluation: {G} models (hidden_dim {a0.hidden_dim}) in one group =======')
     start_time = time.time()
     models = [tr['models'][f].cuda() for tr, f in members]
-    trainer = FusionGroupTrainer(models, lr=[tr['args'].lr for tr, _ in members], weight_decay=[tr['args'].l2 for tr, _ in members],
-                                 grad_clip=[m.model.grad_clip for m in models],
-                                 seeds=[dropout_seed(tr['seed'], f) for tr, f in members], batch_size=B)
-    trainer.set_tables(*tables, emo_all, val_all)
+    trainer = Trainer(models, lr=[tr['args'].lr for tr, _ in members], weight_decay=[tr['args'].l2 for tr, _ in members],
+                      grad_clip=[m.model.grad_clip for m in models], seeds=[dropout_seed(tr['seed'], f) for tr, f in members],
+                      batch_size=B)
+    upload(trainer)
     tests = [np.arange(offs[j + 1], offs[j + 2]) for j in range(n_tests)]
     stores = [[] for _ in range(G)]
     metrics = [[] for _ in range(G)]

@@ -1,7 +1,8 @@
 """Data_Feat_TOPN — the dataset behind `--model attention_topn`: mirror of MER2024/toolkit/data/feat_data_topn.py:9-96.
 
 For `--fusion_topn n --fusion_modality AVT|AV|AT|VT` it loads the n best-ranked utterance-level feature sets of each of three
-modality slots (MER2024/toolkit/globals.py:218-231: the ranking of the MER2024 baseline paper, low to high), time-averages each
+modality slots (MER2024/toolkit/globals.py:218-231: the ranking of the MER2024 baseline paper, low to high; MER2025 and
+MER2026 have rankings of their own, toolkit/globals.py: TOPN_RANK_LOW2HIGH), time-averages each
 clip's feature and hands the model `feat0 .. feat{3n-1}`.  One deliberate difference: the reference decides between the
 `<model>_UTT` and `<model>-UTT` directory spellings by probing the SIMS corpus' feature root whatever the dataset
 (MER2024/toolkit/utils/functions.py:246-253); here the probe looks under the dataset's own feature root."""
@@ -13,19 +14,19 @@ import torch
 from torch.utils.data import Dataset
 
 from ... import config
-from ..globals import AUDIO_RANK_LOW2HIGH, FEATURE_DIR_OF, IMAGE_RANK_LOW2HIGH, TEXT_RANK_LOW2HIGH
+from ..globals import FEATURE_DIR_OF, TOPN_RANK_LOW2HIGH
 from ..utils.read_data import func_read_multiprocess
 
 _SLOTS = {'AVT': ('A', 'T', 'V'), 'AT': ('A', 'T', 'T'), 'AV': ('A', 'V', 'V'), 'VT': ('T', 'T', 'V')}   # reference :17-24
-_RANK = {'A': AUDIO_RANK_LOW2HIGH, 'T': TEXT_RANK_LOW2HIGH, 'V': IMAGE_RANK_LOW2HIGH}
 
 
-def topn_feature_names(topn, modality, feat_root=None, suffix='UTT'):
-    """Directory names of the 3 * topn feature sets, in model-input order."""
+def topn_feature_names(topn, modality, feat_root=None, suffix='UTT', dataset='MER2024'):
+    """Directory names of the 3 * topn feature sets, in model-input order, by `dataset`'s ranking (MER2024 | MER2025 | MER2026)."""
     assert topn is not None and modality in _SLOTS
+    rank = TOPN_RANK_LOW2HIGH[dataset]
     names = []
     for slot in _SLOTS[modality]:
-        names.extend(_RANK[slot][-topn:])
+        names.extend(rank[slot][-topn:])
     assert len(names) == topn * 3
     out = []
     for display in names:
@@ -39,7 +40,7 @@ class Data_Feat_TOPN(Dataset):
     def __init__(self, args, names, labels):
         self.names, self.labels = names, labels
         feat_root = config.PATH_TO_FEATURES[args.dataset]
-        featnames = topn_feature_names(args.fusion_topn, args.fusion_modality, feat_root)
+        featnames = topn_feature_names(args.fusion_topn, args.fusion_modality, feat_root, dataset=args.dataset)
         print(f'feature number: {len(featnames)}')
         self.feat_type, self.feat_scale = args.feat_type, args.feat_scale
         assert self.feat_scale == 1 and self.feat_type == 'utt'

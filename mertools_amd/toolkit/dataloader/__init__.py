@@ -1,9 +1,9 @@
 """get_dataloaders(args) — mirror of MERBench/toolkit/dataloader/__init__.py:14-42 (MER2024/toolkit/dataloader/__init__.py for
-the MER2024 entry) for the corpora on the hot path.  Other corpora keep the same pattern and are out of scope."""
+the MER2024 entry, MER2026/MER2026_Track1/toolkit/dataloader/__init__.py for MER2025 / MER2026) for the corpora on the hot path.  Other corpora keep the same pattern and are out of scope."""
 from .mer2023 import MER2023
-from .mer2024 import MER2024
+from .mer2024 import MER2024, MER2025, MER2026
 
-DATALOADER_MAP = {'MER2023': MER2023, 'MER2024': MER2024}
+DATALOADER_MAP = {'MER2023': MER2023, 'MER2024': MER2024, 'MER2025': MER2025, 'MER2026': MER2026}
 
 
 class get_dataloaders:

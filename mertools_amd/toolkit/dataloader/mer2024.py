@@ -37,8 +37,10 @@ def emotion_metrics(emo_probs, emo_labels):
 
 
 class MER2024(MER2023):
+    DATASET = 'MER2024'
+
     def __init__(self, args):
-        assert args.dataset in ['MER2024']
+        assert args.dataset in [self.DATASET]
         self.args, self.dataset, self.debug = args, args.dataset, args.debug
         self.batch_size, self.num_workers = args.batch_size, args.num_workers
         self.label_path = config.PATH_TO_LABEL[args.dataset]
@@ -68,3 +70,13 @@ class MER2024(MER2023):
 
     def calculate_results(self, emo_probs=[], emo_labels=[], val_preds=[], val_labels=[]):
         return emotion_metrics(emo_probs, emo_labels)
+
+
+# MER2025 / MER2026 (MER2025/MER2025_Track1/toolkit/dataloader/mer2025.py, MER2026/MER2026_Track1/toolkit/dataloader/mer2026.py):
+# the reference's files are mer2024.py with the class name and the dataset assert changed
+class MER2025(MER2024):
+    DATASET = 'MER2025'
+
+
+class MER2026(MER2024):
+    DATASET = 'MER2026'

@@ -13,7 +13,23 @@ TEXT_RANK_LOW2HIGH = ['XLNet-base', 'ELECTRA-large', 'MOSS-7B', 'PERT-large', 'P
                       'RoBERTa-base', 'MacBERT-base', 'RoBERTa-large', 'ChatGLM2-6B', 'MacBERT-large', 'BLOOM-7B', 'Baichuan-13B']
 IMAGE_RANK_LOW2HIGH = ['VideoMAE-base', 'EmoNet', 'VideoMAE-large', 'DINOv2-large', 'SENet-FER2013', 'ResNet-FER2013', 'MANet-RAFDB',
                        'EVA-02-base', 'CLIP-base', 'VideoMAE-base (VoxCeleb2)', 'VideoMAE-base (MER2023)', 'CLIP-large']
+# MER2025 / MER2026 keep shorter rankings of their own (MER2025/MER2025_Track1/toolkit/globals.py:218-242,
+# MER2026/MER2026_Track1/toolkit/globals.py:217-239); Data_Feat_TOPN picks the table of args.dataset.
+TOPN_RANK_LOW2HIGH = {
+    'MER2024': {'A': AUDIO_RANK_LOW2HIGH, 'T': TEXT_RANK_LOW2HIGH, 'V': IMAGE_RANK_LOW2HIGH},
+    'MER2025': {
+        'A': ['WavLM-base', 'wav2vec 2.0-large', 'wav2vec 2.0-base', 'Whisper-large', 'HUBERT-base', 'HUBERT-large'],
+        'T': ['MacBERT-base', 'MacBERT-large', 'BLOOM-7B', 'RoBERTa-large', 'RoBERTa-base'],
+        'V': ['ResNet-FER2013', 'DINOv2-large', 'SENet-FER2013', 'MANet-RAFDB', 'CLIP-base', 'CLIP-large'],
+    },
+    'MER2026': {
+        'A': ['WavLM-base', 'wav2vec 2.0-base', 'wav2vec 2.0-large', 'HUBERT-large', 'HUBERT-base'],
+        'T': ['RoBERTa-base', 'RoBERTa-large', 'MacBERT-base', 'MacBERT-large'],
+        'V': ['VideoMAE-large', 'ResNet-FER2013', 'EmoNet', 'SENet-FER2013', 'CLIP-base', 'CLIP-large'],
+    },
+}
 FEATURE_DIR_OF = {
+    'WavLM-base': 'wavlm-base',
     'eGeMAPS': 'eGeMAPS', 'VGGish': 'vggish', 'Whisper-base': 'whisper-base', 'emotion2vec': 'emotion2vec', 'Whisper-large': 'whisper-large-v2',
     'wav2vec 2.0-base': 'chinese-wav2vec2-base', 'wav2vec 2.0-large': 'chinese-wav2vec2-large', 'HUBERT-base': 'chinese-hubert-base',
     'HUBERT-large': 'chinese-hubert-large',

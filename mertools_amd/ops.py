@@ -146,53 +146,80 @@ def gemm16_raw(args: GemmArgs):
     _lib.check(_lib.lib().mer_gemm16(args, stream()), "mer_gemm16")
 
 
-def layernorm(x, gamma, beta, eps, *, act=None, out32=True, out16=False, out16_lo=False, dtype="f16", M=None, D=None, ldx=None):
+def _ld(t, dense):
+    """Row stride of a caller-supplied 2-D output (a view of a wider buffer is fine), or the dense value when there is none."""
+    return t.stride(0) if t is not None else dense
+
+
+def layernorm(x, gamma, beta, eps, *, act=None, out32=True, out16=False, out16_lo=False, dtype="f16", M=None, D=None, ldx=None, out=None):
+    """out: optional caller-owned (o32, hi, lo) [M, D] views (any of them None); their row strides become ld32 / ld16 (hi and lo
+    share ld16)."""
     D = D if D is not None else x.shape[-1]
     M = M if M is not None else x.numel() // D
     ldx = ldx if ldx is not None else D
     dev = x.device
-    o32 = torch.empty((M, D), dtype=torch.float32, device=dev) if out32 else None
-    oh = torch.empty((M, D), dtype=torch16(dtype), device=dev) if out16 else None
-    ol = torch.empty((M, D), dtype=torch16(dtype), device=dev) if (out16 and out16_lo) else None
-    _lib.check(_lib.lib().mer_layernorm(_p(x), ldx, _p(gamma), _p(beta), eps, M, D, ACT[act], _p(o32), D, _p(oh), _p(ol), D,
+    if out is not None:
+        o32, oh, ol = out
+        assert ol is None or (oh is not None and ol.stride(0) == oh.stride(0))
+    else:
+        o32 = torch.empty((M, D), dtype=torch.float32, device=dev) if out32 else None
+        oh = torch.empty((M, D), dtype=torch16(dtype), device=dev) if out16 else None
+        ol = torch.empty((M, D), dtype=torch16(dtype), device=dev) if (out16 and out16_lo) else None
+    _lib.check(_lib.lib().mer_layernorm(_p(x), ldx, _p(gamma), _p(beta), eps, M, D, ACT[act], _p(o32), _ld(o32, D), _p(oh), _p(ol), _ld(oh, D),
                                         dt_code(dtype), stream()), "mer_layernorm")
     return o32, oh, ol
 
 
-def attention_f32(qkv32, B, T, H, scale, *, kv_len=None, out_lo=True, dtype="f16"):
+def attention_f32(qkv32, B, T, H, scale, *, kv_len=None, out_lo=True, dtype="f16", out=None):
     """qkv32: fp32 [B*T, 3*H*64] (q | k | v column blocks) -> ctx hi (+ lo) 16-bit planes [B*T, H*64] on the exact fp32 MFMA
     (mer_attention_f32: the "accurate" preset's attention)."""
     D = H * 64
     assert qkv32.dtype == torch.float32 and qkv32.shape == (B * T, 3 * D) and qkv32.is_contiguous()
-    oh = torch.empty((B * T, D), dtype=torch16(dtype), device=qkv32.device)
-    ol = torch.empty_like(oh) if out_lo else None
+    if out is not None:
+        oh, ol = out
+        assert ol is None or ol.stride(0) == oh.stride(0)
+    else:
+        oh = torch.empty((B * T, D), dtype=torch16(dtype), device=qkv32.device)
+        ol = torch.empty_like(oh) if out_lo else None
     _lib.check(_lib.lib().mer_attention_f32(qkv32.data_ptr(), qkv32.data_ptr() + D * 4, qkv32.data_ptr() + 2 * D * 4, 3 * D,
-                                            _p(oh), _p(ol), D, B, T, H, float(scale), _p(kv_len), dt_code(dtype), stream()), "mer_attention_f32")
+                                            _p(oh), _p(ol), oh.stride(0), B, T, H, float(scale), _p(kv_len), dt_code(dtype), stream()), "mer_attention_f32")
     return oh, ol
 
 
-def attention(qkv, B, T, H, scale, *, kv_len=None, out_lo=False):
-    """qkv: 16-bit [B*T, 3*H*64] (q | k | v column blocks) -> ctx 16-bit [B*T, H*64]."""
+def attention(qkv, B, T, H, scale, *, kv_len=None, out_lo=False, out=None):
+    """qkv: 16-bit [B*T, 3*H*64] (q | k | v column blocks) -> ctx 16-bit [B*T, H*64].  out: optional caller-owned (hi, lo) [B*T, H*64]
+    views (lo may be None) whose row stride becomes ldo — the same argument on every attention wrapper below."""
     D = H * 64
     assert qkv.shape == (B * T, 3 * D) and qkv.is_contiguous()
-    oh = torch.empty((B * T, D), dtype=qkv.dtype, device=qkv.device)
-    ol = torch.empty_like(oh) if out_lo else None
+    if out is not None:
+        oh, ol = out
+        assert ol is None or ol.stride(0) == oh.stride(0)
+    else:
+        oh = torch.empty((B * T, D), dtype=qkv.dtype, device=qkv.device)
+        ol = torch.empty_like(oh) if out_lo else None
     es = qkv.element_size()
     _lib.check(_lib.lib().mer_attention(qkv.data_ptr(), qkv.data_ptr() + D * es, qkv.data_ptr() + 2 * D * es, 3 * D,
-                                        _p(oh), _p(ol), D, B, T, H, float(scale), _p(kv_len), dt_code(qkv.dtype), stream()),
+                                        _p(oh), _p(ol), oh.stride(0), B, T, H, float(scale), _p(kv_len), dt_code(qkv.dtype), stream()),
                "mer_attention")
     return oh, ol
 
 
-def attention_cls(q, qkv, B, T, H, scale, *, kv_len=None):
-    """One query per sequence: q 16-bit [B, H*64], keys / values from qkv [B*T, 3*H*64] -> ctx 16-bit [B, H*64] (mer_attention_cls)."""
+def attention_cls(q, qkv, B, T, H, scale, *, kv_len=None, out_lo=False, out=None):
+    """One query per sequence: q 16-bit [B, H*64], keys / values from qkv [B*T, 3*H*64] -> ctx 16-bit [B, H*64] (mer_attention_cls).
+    q and qkv may be column slices of wider buffers (their row strides are passed as ldq / ld); with out_lo or out= the result is
+    the (hi, lo) pair."""
     D = H * 64
-    assert qkv.shape == (B * T, 3 * D) and qkv.is_contiguous() and q.shape == (B, D) and q.is_contiguous()
-    oh = torch.empty((B, D), dtype=qkv.dtype, device=qkv.device)
+    assert qkv.shape == (B * T, 3 * D) and qkv.stride(1) == 1 and q.shape == (B, D) and q.stride(1) == 1
+    if out is not None:
+        oh, ol = out
+        assert ol is None or ol.stride(0) == oh.stride(0)
+    else:
+        oh = torch.empty((B, D), dtype=qkv.dtype, device=qkv.device)
+        ol = torch.empty_like(oh) if out_lo else None
     es = qkv.element_size()
-    _lib.check(_lib.lib().mer_attention_cls(q.data_ptr(), D, qkv.data_ptr() + D * es, qkv.data_ptr() + 2 * D * es, 3 * D, _p(oh), None, D,
-                                            B, T, H, float(scale), _p(kv_len), dt_code(qkv.dtype), stream()), "mer_attention_cls")
-    return oh
+    _lib.check(_lib.lib().mer_attention_cls(q.data_ptr(), q.stride(0), qkv.data_ptr() + D * es, qkv.data_ptr() + 2 * D * es, qkv.stride(0), _p(oh), _p(ol),
+                                            oh.stride(0), B, T, H, float(scale), _p(kv_len), dt_code(qkv.dtype), stream()), "mer_attention_cls")
+    return (oh, ol) if (out_lo or out is not None) else oh
 
 
 def wave_normalize(x, do_normalize=True):
@@ -230,14 +257,14 @@ def add_pos(x, pos):
     return x
 
 
-def attention_bias(qkv, B, T, H, scale, bias, *, gate=None, kv_len=None):
+def attention_bias(qkv, B, T, H, scale, bias, *, gate=None, kv_len=None, out=None):
     """attention() with scores += gate[b,h,q] * bias[h,q,k].  bias: fp32 [H, T, ldb] (ldb % 4 == 0), gate: fp32 [B,H,T] or None."""
     D = H * 64
     assert qkv.shape == (B * T, 3 * D) and qkv.is_contiguous() and bias.is_contiguous() and bias.shape[:2] == (H, T)
-    oh = torch.empty((B * T, D), dtype=qkv.dtype, device=qkv.device)
+    oh = out[0] if out is not None else torch.empty((B * T, D), dtype=qkv.dtype, device=qkv.device)
     es = qkv.element_size()
     _lib.check(_lib.lib().mer_attention_bias(qkv.data_ptr(), qkv.data_ptr() + D * es, qkv.data_ptr() + 2 * D * es, 3 * D,
-                                             _p(oh), None, D, B, T, H, float(scale), _p(kv_len), _p(bias), bias.shape[2], _p(gate),
+                                             _p(oh), None, oh.stride(0), B, T, H, float(scale), _p(kv_len), _p(bias), bias.shape[2], _p(gate),
                                              dt_code(qkv.dtype), stream()), "mer_attention_bias")
     return oh
 
@@ -249,15 +276,19 @@ def wavlm_gate(x, w, b, const, B, T, H):
     return gate
 
 
-def attention_hm(qkv_hm, B, T, H, scale, *, kv_len=None, out_lo=False):
+def attention_hm(qkv_hm, B, T, H, scale, *, kv_len=None, out_lo=False, out=None):
     """qkv_hm: 16-bit [3, B, H, T, 64] (head-major, as written by gemm16(headmajor=(T, H))) -> ctx [B*T, H*64]."""
     D = H * 64
     assert qkv_hm.numel() == 3 * B * T * D and qkv_hm.is_contiguous()
-    oh = torch.empty((B * T, D), dtype=qkv_hm.dtype, device=qkv_hm.device)
-    ol = torch.empty_like(oh) if out_lo else None
+    if out is not None:
+        oh, ol = out
+        assert ol is None or ol.stride(0) == oh.stride(0)
+    else:
+        oh = torch.empty((B * T, D), dtype=qkv_hm.dtype, device=qkv_hm.device)
+        ol = torch.empty_like(oh) if out_lo else None
     plane = B * T * D * qkv_hm.element_size()
     _lib.check(_lib.lib().mer_attention_hm(qkv_hm.data_ptr(), qkv_hm.data_ptr() + plane, qkv_hm.data_ptr() + 2 * plane, _p(oh), _p(ol),
-                                           D, B, T, H, float(scale), _p(kv_len), dt_code(qkv_hm.dtype), stream()), "mer_attention_hm")
+                                           oh.stride(0), B, T, H, float(scale), _p(kv_len), dt_code(qkv_hm.dtype), stream()), "mer_attention_hm")
     return oh, ol
 
 
@@ -275,10 +306,15 @@ def hubert_conv0_gn(wav, w, gamma, beta, eps=1e-5, *, stride=5, dtype="f16", lo=
     return oh, ol
 
 
-def posconv_pack(x, G, K, *, dtype="f16", lo=False):
+def posconv_pack(x, G, K, *, dtype="f16", lo=False, valid_frames=None):
+    """valid_frames: int32 [B] — frames >= valid_frames[b] of row b are packed as zeros (mer_posconv_pack_ragged)."""
     B, T, D = x.shape
     oh = torch.empty((B, G, T + K, D // G), dtype=torch16(dtype), device=x.device)
     ol = torch.empty_like(oh) if lo else None
+    if valid_frames is not None:
+        _lib.check(_lib.lib().mer_posconv_pack_ragged(_p(x), B, T, D, G, K, _p(oh), _p(ol), dt_code(dtype), _p(valid_frames), stream()),
+                   "mer_posconv_pack_ragged")
+        return oh, ol
     _lib.check(_lib.lib().mer_posconv_pack(_p(x), B, T, D, G, K, _p(oh), _p(ol), dt_code(dtype), stream()), "mer_posconv_pack")
     return oh, ol
 
@@ -291,22 +327,84 @@ def vit_patchify(px, P, *, dtype="f16", lo=False):
     return oh, ol
 
 
-def vit_assemble(patch, cls, pos, gamma, beta, eps, N, P, D):
+def vit_assemble(patch, cls, pos, gamma, beta, eps, N, P, D, *, dtype="f16", out16=False, out16_lo=False):
+    """-> fp32 [N*(P+1), D]; with out16 the (fp32, hi, lo) triple (lo None unless out16_lo)."""
     out = torch.empty((N * (P + 1), D), dtype=torch.float32, device=patch.device)
-    _lib.check(_lib.lib().mer_vit_assemble(_p(patch), _p(cls), _p(pos), _p(gamma), _p(beta), eps, N, P, D, _p(out), None, None,
-                                           MER_DT_F16, stream()), "mer_vit_assemble")
-    return out
+    oh = torch.empty((N * (P + 1), D), dtype=torch16(dtype), device=patch.device) if out16 else None
+    ol = torch.empty_like(oh) if (out16 and out16_lo) else None
+    _lib.check(_lib.lib().mer_vit_assemble(_p(patch), _p(cls), _p(pos), _p(gamma), _p(beta), eps, N, P, D, _p(out), _p(oh), _p(ol),
+                                           dt_code(dtype), stream()), "mer_vit_assemble")
+    return (out, oh, ol) if out16 else out
 
 
-def bert_embed(ids, token_type, word, pos, type_emb, pos_mode, pad_id, gamma, beta, eps, *, dtype="f16"):
+def bert_embed(ids, token_type, word, pos, type_emb, pos_mode, pad_id, gamma, beta, eps, *, dtype="f16", out16_lo=False):
     B, T = ids.shape
     D = word.shape[1]
     o32 = torch.empty((B * T, D), dtype=torch.float32, device=ids.device)
     oh = torch.empty((B * T, D), dtype=torch16(dtype), device=ids.device)
+    ol = torch.empty_like(oh) if out16_lo else None
     _lib.check(_lib.lib().mer_bert_embed(_p(ids), _p(token_type), B, T, D, _p(word), _p(pos), _p(type_emb), pos_mode, pad_id,
-                                         _p(gamma), _p(beta), eps, _p(o32), _p(oh), None, dt_code(dtype), stream()),
+                                         _p(gamma), _p(beta), eps, _p(o32), _p(oh), _p(ol), dt_code(dtype), stream()),
                "mer_bert_embed")
-    return o32, oh
+    return (o32, oh, ol) if out16_lo else (o32, oh)
+
+
+def video_patchify(px, P, ts, *, dtype="f16", lo=False):
+    """fp32 [B, F, C, H, W] -> tubelet rows [B*(F/ts)*(H/P)*(W/P), C*ts*P*P] as 16-bit planes (mer_video_patchify)."""
+    B, Fr, Cc, H, W = px.shape
+    assert px.is_contiguous() and px.dtype == torch.float32
+    oh = torch.empty((B * (Fr // ts) * (H // P) * (W // P), Cc * ts * P * P), dtype=torch16(dtype), device=px.device)
+    ol = torch.empty_like(oh) if lo else None
+    _lib.check(_lib.lib().mer_video_patchify(_p(px), B, Fr, Cc, H, W, P, ts, _p(oh), _p(ol), dt_code(dtype), stream()), "mer_video_patchify")
+    return oh, ol
+
+
+def swiglu(y, F, *, dtype="f16", lo=False):
+    """y fp32 [M, >= 2F] (row stride = ldy; gate half in columns [0, F), linear half in [F, 2F)) -> silu(gate) * linear as 16-bit
+    planes [M, F] (mer_swiglu)."""
+    assert y.dim() == 2 and y.dtype == torch.float32 and y.stride(1) == 1 and y.shape[1] >= 2 * F
+    M = y.shape[0]
+    oh = torch.empty((M, F), dtype=torch16(dtype), device=y.device)
+    ol = torch.empty_like(oh) if lo else None
+    _lib.check(_lib.lib().mer_swiglu(_p(y), y.stride(0), M, F, _p(oh), _p(ol), dt_code(dtype), stream()), "mer_swiglu")
+    return oh, ol
+
+
+def token_reduce(x, scale=1.0):
+    """x fp32 [N, T, D] -> scale * x.sum(1), fp32 [N, D] (mer_token_reduce)."""
+    assert x.dim() == 3 and x.dtype == torch.float32 and x.is_contiguous()
+    N, T, D = x.shape
+    out = torch.empty((N, D), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().mer_token_reduce(_p(x), N, T, D, float(scale), _p(out), stream()), "mer_token_reduce")
+    return out
+
+
+def hubert_conv0_plain(wav, w, bias=None, *, stride=5):
+    """wav fp32 [B, L], w fp32 [C, k] -> bias + conv1d, fp32 channels-last [B, T0, C] (mer_hubert_conv0_plain)."""
+    B, L = wav.shape
+    Cc, k = w.shape
+    assert wav.is_contiguous() and w.is_contiguous()
+    T0 = (L - k) // stride + 1
+    out = torch.empty((B, T0, Cc), dtype=torch.float32, device=wav.device)
+    _lib.check(_lib.lib().mer_hubert_conv0_plain(_p(wav), B, L, _p(w), _p(bias), Cc, k, stride, _p(out), stream()), "mer_hubert_conv0_plain")
+    return out
+
+
+def hubert_valid_frames(valid_samples, L, kernels, strides, *, all_layers=False):
+    """valid_samples int32 [B] -> (t0_len, tn_len) int32 [B] each (mer_hubert_valid_frames), or with all_layers the counts after
+    every conv, int32 [n_conv, B] (mer_hubert_valid_frames_all)."""
+    import ctypes
+    assert valid_samples.dtype == torch.int32 and valid_samples.is_contiguous() and len(kernels) == len(strides)
+    B, n = valid_samples.numel(), len(kernels)
+    ks, ss = (ctypes.c_int * n)(*kernels), (ctypes.c_int * n)(*strides)
+    if all_layers:
+        lens = torch.empty((n, B), dtype=torch.int32, device=valid_samples.device)
+        _lib.check(_lib.lib().mer_hubert_valid_frames_all(_p(valid_samples), B, int(L), n, ks, ss, _p(lens), stream()), "mer_hubert_valid_frames_all")
+        return lens
+    t0 = torch.empty((B,), dtype=torch.int32, device=valid_samples.device)
+    tn = torch.empty_like(t0)
+    _lib.check(_lib.lib().mer_hubert_valid_frames(_p(valid_samples), B, int(L), n, ks, ss, _p(t0), _p(tn), stream()), "mer_hubert_valid_frames")
+    return t0, tn
 
 
 def sum_pool(hs, seg_start=None, seg_len=None, *, frames=False):

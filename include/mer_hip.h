@@ -316,7 +316,7 @@ int mer_adam_step_dev(float* p, const float* g, float* m, float* v, long long n,
                       float weight_decay, int* step_dev, float clip_value, mer_stream_t stream);
 int mer_inc_i32(int* x, mer_stream_t stream);
 
-/* ---- grouped fusion training (csrc/fusion_group.hip): G independent Attention models (feat_type utt, emotion + valence
+/* ---- grouped fusion training (the 3-stream ABI of the group engine, csrc/fusion_topn_group.hip): G independent Attention models (feat_type utt, emotion + valence
  *      heads, MERBench/toolkit/models/attention.py:36-57) — e.g. the 5 folds of a CV run times N trials — trained in ONE
  *      step whose launch count does not depend on G.  Parameters / gradients / Adam moments are [G, P] fp32, each row in
  *      model.parameters() order: {audio, text, video}_encoder.linear_{1,2,3}.{weight, bias}, attention_mlp.linear_{1,2,3},
@@ -326,7 +326,7 @@ int mer_inc_i32(int* x, mer_stream_t stream);
  *      the step's last launch advances *cursor, so a captured step replays through an epoch's [n_steps, G, B] table.
  *      Model g's results are bitwise those of a group holding g alone, and at dropout 0 those of the single-model kernels
  *      (FusionGraphTrainer).  Dropout masks come from a counter-based hash of (seed[g], step[g], site, row, col),
- *      documented in csrc/fusion_group.hip; train steps bump step[g] of every active model.  Eval steps (train = 0): forward
+ *      documented in csrc/fusion_topn_group.hip (the site << 30 layout); train steps bump step[g] of every active model.  Eval steps (train = 0): forward
  *      and losses only, no dropout, counters unchanged.  A step allocates nothing and never synchronises. */
 typedef struct {
   int G, B, n_steps;                 /* models, rows per minibatch (<= 2048), steps in the index / count / out_* tables */

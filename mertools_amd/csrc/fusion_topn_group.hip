@@ -1,17 +1,23 @@
-// fusion_topn_group.hip — one training (or evaluation) step for a GROUP of G independent Attention_TOPN fusion models of one
-// architecture (MER2024/toolkit/models/attention_topn.py: M feature streams, 1 <= M <= 18, feat_type 'utt', an emotion head of
-// C1 classes and a valence head of C2 in {0, 1} outputs): the 5 folds of a cross-validation run times N hyper-parameter trials
-// of the MER2024 / MER2025 / MER2026 multi-feature recipe.  The design rules are fusion_group.hip's: the model index is a grid
-// axis of every launch and the M streams are entries of grouped problem lists, so the number of launches of a step depends on
-// neither G nor M (25 for a train step with C2 = 0, 26 with C2 = 1, 12 for an eval step); every stage is an ordinary launch on
-// one stream, and a step allocates nothing and never synchronises (graph-capturable).
+// fusion_topn_group.hip — the group engine: one training (or evaluation) step for a GROUP of G independent fusion models of
+// one architecture, the 5 folds of a cross-validation run times N hyper-parameter trials.  Two C ABIs run on it:
+//   mer_fusion_topn_group_*  Attention_TOPN (MER2024/toolkit/models/attention_topn.py: M feature streams, 1 <= M <= 18,
+//                            feat_type 'utt', an emotion head of C1 classes and a valence head of C2 in {0, 1} outputs), the
+//                            MER2024 / MER2025 / MER2026 multi-feature recipe;
+//   mer_fusion_group_*       Attention (MERBench/toolkit/models/attention.py:36-57 with feat_type 'utt', both heads;
+//                            main-release.py:31-66), MER2023: the same model with M = 3 (audio, text, video) and C2 = 1.  Its
+//                            entry points (end of this file) map their descriptor onto the engine's.
+// The model index is a grid axis of every launch and the M streams are entries of grouped problem lists, so the number of
+// launches of a step depends on neither G nor M (25 for a train step with C2 = 0, 26 with C2 = 1, 12 for an eval step);
+// every stage is an ordinary launch on one stream (no inter-workgroup communication), and a step allocates nothing and never
+// synchronises (graph-capturable).
 //
 // Arithmetic contract: each stage is the per-element arithmetic of the single-model kernels (gemm32.hip's MFMA k grouping and
 // epilogue, fusion.hip's fuse forward — an fmaf chain over the streams in stream order — and backward, CE / MSE rows and their
 // in-order means, Adam), with the row count of a model (n_g <= B) taking the place of the minibatch size.  So model g's losses,
 // outputs, gradients and parameters are bitwise those of a group holding g alone, and for M = 3, C2 = 1, dropout 0 bitwise
-// those of fusion_group.hip on the same flat parameters.  With C2 = 0 the loss is CE alone and there is no valence output or
-// gradient.  A model with n_g = 0 is idle: its parameters, gradients, Adam moments and step counter are not touched.
+// those of FusionGraphTrainer on the same minibatches, through either ABI.  With C2 = 0 the loss is CE alone and there is no
+// valence output or gradient.  A model with n_g = 0 is idle: its parameters, gradients, Adam moments and step counter are not
+// touched.
 //
 // Problem lists travel by value as kernel arguments.  A list holds up to 3 * 18 + 6 = 60 problems (the weight gradients of
 // every Linear of an 18-stream model), so a problem is a compact 64-byte record of offsets into the launch's base pointers
@@ -19,12 +25,15 @@
 // is 3960 bytes, under HIP's 4 KB limit (static_assert below).
 //
 // Dropout keep mask (stateless, counter-based; site i < M = input of encoder i, site M = input of attention_mlp):
-//   ctr  = (uint64(uint32(step)) << 32) | (site << 27) | (row << 16) | col     (site < 32, row < 2^11, col < 2^16)
+//   ctr  = (uint64(uint32(step)) << 32) | (site << shift) | (row << 16) | col
 //   z    = seed + (ctr + 1) * 0x9E3779B97F4A7C15                                 (mod 2^64)
 //   z    = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z ^= z >> 31   (splitmix64)
 //   u    = float(z >> 40) * 2^-24;   keep = u >= p;   out = keep ? x * (1.0f / (1.0f - p)) : 0      (fp32)
-// step is the model's optimiser step counter before the step, row the row within the minibatch.  (The mixer is
-// fusion_group.hip's; only the field widths of the counter differ, because 19 sites do not fit its 2-bit site field.)
+// step is the model's optimiser step counter before the step, row the row within the minibatch.  The two ABIs differ in the
+// field widths of the counter and in nothing else, and each layout is a documented contract with an exact test:
+//   mer_fusion_topn_group_*  shift = 27   (site < 32, row < 2^11, col < 2^16; 19 sites do not fit a 2-bit field)
+//   mer_fusion_group_*       shift = 30   (site 0/1/2 = audio/text/video encoder input, 3 = attention_mlp input; row < 2^14)
+// The shift travels in TgCtx (TgCtx::site_shift) and is an argument of tg_keep and tg_mask_kernel.
 #include "common.h"
 
 namespace mer {
@@ -37,7 +46,9 @@ struct TgCtx {
   const int* cursor;
   const int* count;
   int G, B, S;
+  int site_shift;   // dropout counter layout: 27 (mer_fusion_topn_group_*) or 30 (mer_fusion_group_*)
 };
+static_assert(sizeof(TgCtx) == 32, "site_shift lives in TgCtx's tail padding");
 
 // rows of model g in the current step (0 = idle; also 0 once the cursor ran past the step table)
 __device__ __forceinline__ int tg_rows(const TgCtx& c, int g) {
@@ -55,8 +66,8 @@ __host__ __device__ __forceinline__ uint64_t tg_mix(uint64_t z) {
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   return z ^ (z >> 31);
 }
-__device__ __forceinline__ bool tg_keep(uint64_t seed, int step, int site, int row, int col, float p) {
-  const uint64_t ctr = ((uint64_t)(uint32_t)step << 32) | ((uint64_t)site << 27) | ((uint64_t)row << 16) | (uint64_t)col;
+__device__ __forceinline__ bool tg_keep(uint64_t seed, int step, int site, int row, int col, float p, int shift) {
+  const uint64_t ctr = ((uint64_t)(uint32_t)step << 32) | ((uint64_t)site << shift) | ((uint64_t)row << 16) | (uint64_t)col;
   const uint64_t z = tg_mix(seed + (ctr + 1ull) * 0x9E3779B97F4A7C15ull);
   return (float)(z >> 40) * (1.0f / 16777216.0f) >= p;
 }
@@ -88,7 +99,7 @@ __global__ __launch_bounds__(256) void tg_gather_kernel(TgCtx c, const TgTabs T,
     float* dst = w + T.o_x[e] + (long long)r * D;
     for (int j = threadIdx.x; j < D; j += blockDim.x) {
       const float x = ok ? tab[src * D + j] : 0.f;
-      dst[j] = p > 0.f ? (tg_keep(sd, st, e, r, j, p) ? x * scale : 0.f) : x;
+      dst[j] = p > 0.f ? (tg_keep(sd, st, e, r, j, p, c.site_shift) ? x * scale : 0.f) : x;
     }
   }
   if (threadIdx.x == 0) {
@@ -197,7 +208,7 @@ __global__ __launch_bounds__(256) void tg_dropout_kernel(TgCtx c, float* ws, lon
   const uint64_t sd = seed ? seed[g] : 0ull;
   const int st = step[g];
   for (int j = threadIdx.x; j < W; j += blockDim.x)
-    y[j] = p > 0.f ? (tg_keep(sd, st, site, r, j, p) ? x[j] * scale : 0.f) : x[j];
+    y[j] = p > 0.f ? (tg_keep(sd, st, site, r, j, p, c.site_shift) ? x[j] * scale : 0.f) : x[j];
 }
 
 // ---- fuse_fwd: feat[b,j] = sum_e mh[b, e*H + j] * att[b,e] (fmaf chain, e in stream order).  grid (B, G) ----
@@ -311,7 +322,7 @@ __global__ __launch_bounds__(256) void tg_mh_bwd_kernel(TgCtx c, float* ws, long
   const int st = step[g];
   for (int j = threadIdx.x; j < W; j += blockDim.x) {
     const float dx = base[o_dxa + o + j];
-    const float dd = p > 0.f ? (tg_keep(sd, st, site, r, j, p) ? dx * scale : 0.f) : dx;
+    const float dd = p > 0.f ? (tg_keep(sd, st, site, r, j, p, c.site_shift) ? dx * scale : 0.f) : dx;
     const float dy = base[o_dhf + o + j] + dd;
     base[o_dz + o + j] = base[o_mh + o + j] > 0.f ? dy : 0.f;
   }
@@ -376,10 +387,11 @@ __global__ __launch_bounds__(256) void tg_finish_kernel(TgCtx c, int* step, int 
   if (threadIdx.x == 0 && cursor) *cursor += 1;
 }
 
-__global__ __launch_bounds__(256) void tg_mask_kernel(uint64_t seed, int step, int site, int rows, int cols, float p, uint8_t* keep) {
+__global__ __launch_bounds__(256) void tg_mask_kernel(uint64_t seed, int step, int site, int rows, int cols, float p, uint8_t* keep,
+                                                      int shift) {
   const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
   if (i >= (long long)rows * cols) return;
-  keep[i] = tg_keep(seed, step, site, (int)(i / cols), (int)(i % cols), p) ? 1 : 0;
+  keep[i] = tg_keep(seed, step, site, (int)(i / cols), (int)(i % cols), p, shift) ? 1 : 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -504,23 +516,24 @@ extern "C" long long mer_fusion_topn_group_workspace_bytes(const mer_fusion_topn
   return (long long)d->G * tg_layout(*d).stride * (long long)sizeof(float);
 }
 
-extern "C" int mer_fusion_topn_group_step(const mer_fusion_topn_group* d, int train, mer_stream_t stream) {
-  const int rc = tg_check_shape("mer_fusion_topn_group_step", d);
+// One step of the engine for either ABI: `fn` names the entry point in every error, `site_shift` is its dropout counter layout.
+static int tg_step(const char* fn, const mer_fusion_topn_group* d, int site_shift, int train, mer_stream_t stream) {
+  const int rc = tg_check_shape(fn, d);
   if (rc != MER_OK) return rc;
   const int G = d->G, B = d->B, H = d->H, C1 = d->C1, C2 = d->C2, M = d->M;
   const TgPar Pr = tg_params(M, d->D, H, C1, C2);
   const TgLay Ly = tg_layout(*d);
-  MER_REQUIRE(d->P == Pr.P, MER_ESHAPE, "mer_fusion_topn_group_step: P=%lld, the architecture has %lld parameters", d->P, Pr.P);
+  MER_REQUIRE(d->P == Pr.P, MER_ESHAPE, "%s: P=%lld, the architecture has %lld parameters", fn, d->P, Pr.P);
   MER_REQUIRE(d->params && d->emo && d->index && d->count && d->workspace && d->step && d->n_rows > 0 && (C2 == 0 || d->val),
-              MER_EINVAL, "mer_fusion_topn_group_step: null pointer");
-  for (int e = 0; e < M; ++e) MER_REQUIRE(d->feat[e], MER_EINVAL, "mer_fusion_topn_group_step: null feature table %d", e);
+              MER_EINVAL, "%s: null pointer", fn);
+  for (int e = 0; e < M; ++e) MER_REQUIRE(d->feat[e], MER_EINVAL, "%s: null feature table %d", fn, e);
   MER_REQUIRE(d->workspace_bytes >= (long long)G * Ly.stride * (long long)sizeof(float), MER_ENOMEM,
-              "mer_fusion_topn_group_step: workspace of %lld bytes, %lld needed", d->workspace_bytes,
+              "%s: workspace of %lld bytes, %lld needed", fn, d->workspace_bytes,
               (long long)G * Ly.stride * (long long)sizeof(float));
   MER_REQUIRE(!train || (d->grads && d->adam_m && d->adam_v && d->lr && d->weight_decay && d->grad_clip && d->dropout), MER_EINVAL,
-              "mer_fusion_topn_group_step: a train step needs grads, Adam moments and the per-model lr / weight_decay / grad_clip / dropout");
+              "%s: a train step needs grads, Adam moments and the per-model lr / weight_decay / grad_clip / dropout", fn);
   hipStream_t st = (hipStream_t)stream;
-  const TgCtx ctx{d->cursor, d->count, G, B, d->n_steps};
+  const TgCtx ctx{d->cursor, d->count, G, B, d->n_steps, site_shift};
   const long long S = Ly.stride, P = d->P;
   float* ws = (float*)d->workspace;
   float* par = d->params;
@@ -677,13 +690,73 @@ extern "C" int mer_fusion_topn_group_step(const mer_fusion_topn_group* d, int tr
                                                           d->beta1, d->beta2, d->eps, d->step);
   }
   tg_finish_kernel<<<1, 256, 0, st>>>(ctx, d->step, train, d->cursor);
-  return check_launch("fusion_topn_group_step");
+  return check_launch(fn);
+}
+
+extern "C" int mer_fusion_topn_group_step(const mer_fusion_topn_group* d, int train, mer_stream_t stream) {
+  return tg_step("mer_fusion_topn_group_step", d, 27, train, stream);
+}
+
+static int tg_mask(const char* fn, int site_shift, uint64_t seed, int step, int site, int rows, int cols, float p, uint8_t* keep,
+                   mer_stream_t stream) {
+  tg_mask_kernel<<<(unsigned)cdiv((long long)rows * cols, 256), 256, 0, (hipStream_t)stream>>>(seed, step, site, rows, cols, p, keep,
+                                                                                               site_shift);
+  return check_launch(fn);
 }
 
 extern "C" int mer_fusion_topn_group_dropout_mask(uint64_t seed, int step, int site, int rows, int cols, float p, uint8_t* keep,
                                                   mer_stream_t stream) {
   MER_REQUIRE(keep && rows > 0 && cols > 0 && rows <= TG_MAXB && cols < 65536 && site >= 0 && site <= TG_MAXS, MER_EINVAL,
               "mer_fusion_topn_group_dropout_mask: bad args (rows=%d cols=%d site=%d)", rows, cols, site);
-  tg_mask_kernel<<<(unsigned)cdiv((long long)rows * cols, 256), 256, 0, (hipStream_t)stream>>>(seed, step, site, rows, cols, p, keep);
-  return check_launch("fusion_topn_group_dropout_mask");
+  return tg_mask("mer_fusion_topn_group_dropout_mask", 27, seed, step, site, rows, cols, p, keep, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// the 3-stream ABI (mer_fusion_group_*): the engine with M = 3 (audio, text, video), C2 = 1 and the site << 30 counter layout.
+// For M = 3 tg_params is model.parameters() order of the Attention model and tg_layout the workspace this ABI always had.
+// ---------------------------------------------------------------------------------------------------------------------
+static int fg_as_topn(const char* fn, const mer_fusion_group* d, mer_fusion_topn_group* t) {
+  MER_REQUIRE(d, MER_EINVAL, "%s: null descriptor", fn);
+  MER_REQUIRE(d->G > 0 && d->B > 0 && d->B <= TG_MAXB && d->n_steps > 0, MER_ESHAPE,
+              "%s: need G > 0, 0 < B <= %d, n_steps > 0 (G=%d B=%d n_steps=%d)", fn, TG_MAXB, d->G, d->B, d->n_steps);
+  MER_REQUIRE(d->Da > 0 && d->Dt > 0 && d->Dv > 0 && d->H > 0 && d->Da < 65536 && d->Dt < 65536 && d->Dv < 65536 && 3 * d->H < 65536,
+              MER_ESHAPE, "%s: bad dims Da=%d Dt=%d Dv=%d H=%d", fn, d->Da, d->Dt, d->Dv, d->H);
+  MER_REQUIRE(d->C1 > 0 && d->C1 <= 64 && d->C2 == 1, MER_EUNSUPPORTED,
+              "%s: only the emotion (C1 <= 64) + valence (C2 = 1) heads are built (C1=%d C2=%d)", fn, d->C1, d->C2);
+  *t = mer_fusion_topn_group{};
+  t->G = d->G; t->B = d->B; t->n_steps = d->n_steps; t->M = 3; t->H = d->H; t->C1 = d->C1; t->C2 = d->C2; t->P = d->P;
+  t->D[0] = d->Da; t->D[1] = d->Dt; t->D[2] = d->Dv;
+  t->feat[0] = d->feat_a; t->feat[1] = d->feat_t; t->feat[2] = d->feat_v;
+  t->params = d->params; t->grads = d->grads; t->adam_m = d->adam_m; t->adam_v = d->adam_v; t->step = d->step;
+  t->lr = d->lr; t->weight_decay = d->weight_decay; t->grad_clip = d->grad_clip; t->dropout = d->dropout; t->seed = d->seed;
+  t->beta1 = d->beta1; t->beta2 = d->beta2; t->eps = d->eps;
+  t->emo = d->emo; t->val = d->val; t->n_rows = d->n_rows; t->index = d->index; t->count = d->count; t->cursor = d->cursor;
+  t->out_loss = d->out_loss; t->out_emo = d->out_emo; t->out_val = d->out_val;
+  t->workspace = d->workspace; t->workspace_bytes = d->workspace_bytes;
+  return MER_OK;
+}
+
+extern "C" long long mer_fusion_group_param_count(int Da, int Dt, int Dv, int H, int C1, int C2) {
+  if (Da <= 0 || Dt <= 0 || Dv <= 0 || H <= 0 || C1 <= 0 || C2 <= 0) return MER_EINVAL;
+  const int D[3] = {Da, Dt, Dv};
+  return tg_params(3, D, H, C1, C2).P;
+}
+
+extern "C" long long mer_fusion_group_workspace_bytes(const mer_fusion_group* d) {
+  mer_fusion_topn_group t;
+  const int rc = fg_as_topn("mer_fusion_group_workspace_bytes", d, &t);
+  return rc != MER_OK ? rc : (long long)t.G * tg_layout(t).stride * (long long)sizeof(float);
+}
+
+extern "C" int mer_fusion_group_step(const mer_fusion_group* d, int train, mer_stream_t stream) {
+  mer_fusion_topn_group t;
+  const int rc = fg_as_topn("mer_fusion_group_step", d, &t);
+  return rc != MER_OK ? rc : tg_step("mer_fusion_group_step", &t, 30, train, stream);
+}
+
+extern "C" int mer_fusion_group_dropout_mask(uint64_t seed, int step, int site, int rows, int cols, float p, uint8_t* keep,
+                                             mer_stream_t stream) {
+  MER_REQUIRE(keep && rows > 0 && cols > 0 && rows <= 16384 && cols < 65536 && site >= 0 && site < 4, MER_EINVAL,
+              "mer_fusion_group_dropout_mask: bad args (rows=%d cols=%d site=%d)", rows, cols, site);
+  return tg_mask("mer_fusion_group_dropout_mask", 30, seed, step, site, rows, cols, p, keep, stream);
 }

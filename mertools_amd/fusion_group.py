@@ -1,5 +1,6 @@
 """Grouped fusion training: G independent Attention models (the 5 folds of a cross-validation run times N hyper-parameter
-trials) trained by ONE captured step of libmer_hip.so's mer_fusion_group_step (csrc/fusion_group.hip).
+trials) trained by ONE captured step of libmer_hip.so's mer_fusion_group_step (the 3-stream ABI of the group engine,
+csrc/fusion_topn_group.hip).
 
 The minibatches are gathered on the device from split tables uploaded once; an epoch is one [S, G, B] index table and one
 [S, G] row-count table, walked by replaying the captured train / eval step S times (a device cursor the step advances picks
@@ -55,27 +56,54 @@ class FusionGroupTrainer:
         loss, emo, val = tr.run(index, count, train)                # index [S, G, B], count [S, G]; train: bool or [S] bools
     """
 
+    # ---- what a group of another model states (fusion_topn_group.FusionTopnGroupTrainer), besides set_tables ----
+    _ABI = "mer_fusion_group"   # the C entry points: <_ABI>_workspace_bytes and <_ABI>_step on the matching descriptor
+
+    _net = staticmethod(_attention_of)   # the supported network inside a model, or MerError
+
+    @staticmethod
+    def _arch(n):
+        return (n.audio_encoder.linear_1.in_features, n.text_encoder.linear_1.in_features, n.video_encoder.linear_1.in_features,
+                n.fc_att.in_features, n.fc_out_1.out_features, n.fc_out_2.out_features)
+
+    def _set_arch(self, arch):
+        self.Da, self.Dt, self.Dv, self.H, self.C1, self.C2 = arch
+
+    def _param_count(self):
+        return _lib.lib().mer_fusion_group_param_count(self.Da, self.Dt, self.Dv, self.H, self.C1, self.C2)
+
+    @staticmethod
+    def _dropout_p(n):
+        return n.audio_encoder.drop.p
+
+    def _val_shape(self, S):
+        return (S, self.G, self.B)
+
+    def _new_desc(self):
+        """The step descriptor, all but its workspace."""
+        t = self._tables
+        return _lib.FusionGroup(G=self.G, B=self.B, n_steps=self._cap, Da=self.Da, Dt=self.Dt, Dv=self.Dv, H=self.H, C1=self.C1,
+                                C2=self.C2, feat_a=_p(t["a"]), feat_t=_p(t["t"]), feat_v=_p(t["v"]), emo=_p(t["emo"]), val=_p(t["val"]),
+                                out_val=_p(self.out_val), **self._common_fields())
+
+    # ---- the common part ----
     def __init__(self, models, lr, weight_decay, grad_clip, seeds=None, batch_size=32):
+        name = type(self).__name__
         G = len(models)
         if G == 0:
-            raise _lib.MerError("FusionGroupTrainer needs at least one model")
-        nets = [_attention_of(m) for m in models]
-        n0 = nets[0]
-        dims = (n0.audio_encoder.linear_1.in_features, n0.text_encoder.linear_1.in_features, n0.video_encoder.linear_1.in_features,
-                n0.fc_att.in_features, n0.fc_out_1.out_features, n0.fc_out_2.out_features)
+            raise _lib.MerError(f"{name} needs at least one model")
+        nets = [self._net(m) for m in models]
+        arch = self._arch(nets[0])
         for n in nets:
-            d = (n.audio_encoder.linear_1.in_features, n.text_encoder.linear_1.in_features, n.video_encoder.linear_1.in_features,
-                 n.fc_att.in_features, n.fc_out_1.out_features, n.fc_out_2.out_features)
-            if d != dims:
-                raise _lib.MerError(f"a group holds models of one architecture: {d} != {dims}")
-        self.Da, self.Dt, self.Dv, self.H, self.C1, self.C2 = dims
+            if self._arch(n) != arch:
+                raise _lib.MerError(f"a group holds models of one architecture: {self._arch(n)} != {arch}")
+        self._set_arch(arch)
         self.G, self.B = G, int(batch_size)
         self.models = models
-        lib = _lib.lib()
-        P = lib.mer_fusion_group_param_count(self.Da, self.Dt, self.Dv, self.H, self.C1, self.C2)
+        P = self._param_count()
         params0 = [p for p in models[0].parameters() if p.requires_grad]
         if not params0[0].is_cuda:
-            raise _lib.MerError("FusionGroupTrainer needs the models on the GPU (there is no CPU path)")
+            raise _lib.MerError(f"{name} needs the models on the GPU (there is no CPU path)")
         dev = params0[0].device
         if sum(p.numel() for p in params0) != P:
             raise _lib.MerError("parameter count differs from the grouped kernels' layout")
@@ -103,13 +131,14 @@ class FusionGroupTrainer:
         self.lr = torch.tensor(per_model(lr, "lr"), dtype=torch.float32, device=dev)
         self.wd = torch.tensor(per_model(weight_decay, "weight_decay"), dtype=torch.float32, device=dev)
         self.clip = torch.tensor([float(c) for c in per_model(grad_clip, "grad_clip")], dtype=torch.float32, device=dev)
-        self.dropout = torch.tensor([float(n.audio_encoder.drop.p) for n in nets], dtype=torch.float32, device=dev)
+        self.dropout = torch.tensor([float(self._dropout_p(n)) for n in nets], dtype=torch.float32, device=dev)
         seeds = per_model(seeds if seeds is not None else 0, "seeds")   # uint64 bits carried in an int64 tensor
         self.seed = torch.from_numpy(np.array([int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds], dtype=np.uint64).view(np.int64)).to(dev)
         self.cursor = torch.zeros(1, dtype=torch.int32, device=dev)
         self._tables = None
         self._cap = 0
         self._graphs = {}
+        self._ws = None   # sized by (architecture, G, B), which a trainer never changes: allocated once
 
     # ---- data ----
     def set_tables(self, audios, texts, videos, emos, vals):
@@ -133,29 +162,29 @@ class FusionGroupTrainer:
         self.count = torch.zeros((S, G), dtype=torch.int32, device=dev)
         self.out_loss = torch.zeros((S, G), dtype=torch.float32, device=dev)
         self.out_emo = torch.zeros((S, G, B, self.C1), dtype=torch.float32, device=dev)
-        self.out_val = torch.zeros((S, G, B), dtype=torch.float32, device=dev)
+        self.out_val = torch.zeros(self._val_shape(S), dtype=torch.float32, device=dev)
         self._graphs = {}
 
+    def _common_fields(self):
+        """The descriptor fields both ABIs spell alike."""
+        return dict(P=self.P, params=_p(self.flat), grads=_p(self.flat_grad), adam_m=_p(self.m), adam_v=_p(self.v),
+                    step=_p(self.step), lr=_p(self.lr), weight_decay=_p(self.wd), grad_clip=_p(self.clip),
+                    dropout=_p(self.dropout), seed=_p(self.seed), beta1=0.9, beta2=0.999, eps=1e-8,
+                    n_rows=self._tables["a"].shape[0], index=_p(self.index), count=_p(self.count), cursor=_p(self.cursor),
+                    out_loss=_p(self.out_loss), out_emo=_p(self.out_emo))
+
     def _desc(self):
-        t = self._tables
-        d = _lib.FusionGroup(G=self.G, B=self.B, n_steps=self._cap, Da=self.Da, Dt=self.Dt, Dv=self.Dv, H=self.H, C1=self.C1, C2=self.C2,
-                             P=self.P, params=_p(self.flat), grads=_p(self.flat_grad), adam_m=_p(self.m), adam_v=_p(self.v),
-                             step=_p(self.step), lr=_p(self.lr), weight_decay=_p(self.wd), grad_clip=_p(self.clip),
-                             dropout=_p(self.dropout), seed=_p(self.seed), beta1=0.9, beta2=0.999, eps=1e-8,
-                             feat_a=_p(t["a"]), feat_t=_p(t["t"]), feat_v=_p(t["v"]), emo=_p(t["emo"]), val=_p(t["val"]),
-                             n_rows=t["a"].shape[0], index=_p(self.index), count=_p(self.count), cursor=_p(self.cursor),
-                             out_loss=_p(self.out_loss), out_emo=_p(self.out_emo), out_val=_p(self.out_val))
-        if getattr(self, "_ws", None) is None or self._ws_key != (self.G, self.B):
-            nbytes = _lib.lib().mer_fusion_group_workspace_bytes(ctypes.byref(d))
+        d = self._new_desc()
+        if self._ws is None:
+            nbytes = getattr(_lib.lib(), self._ABI + "_workspace_bytes")(ctypes.byref(d))
             if nbytes < 0:
-                _lib.check(int(nbytes), "mer_fusion_group_workspace_bytes")
+                _lib.check(int(nbytes), self._ABI + "_workspace_bytes")
             self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
-            self._ws_key = (self.G, self.B)
         d.workspace, d.workspace_bytes = _p(self._ws), self._ws.numel()
         return d
 
     def _launch(self, d, train):
-        _lib.check(_lib.lib().mer_fusion_group_step(ctypes.byref(d), int(train), stream()), "mer_fusion_group_step")
+        _lib.check(getattr(_lib.lib(), self._ABI + "_step")(ctypes.byref(d), int(train), stream()), self._ABI + "_step")
 
     def _graph(self, train):
         if train not in self._graphs:

@@ -10,7 +10,6 @@ valence output is an empty [S, G, B, 0] tensor.
 """
 import ctypes
 
-import numpy as np
 import torch
 
 from . import _lib
@@ -61,58 +60,33 @@ class FusionTopnGroupTrainer(FusionGroupTrainer):
     run / train_step / eval_step and the captured graphs are FusionGroupTrainer's; the valence output is [S, G, B, C2].
     """
 
-    def __init__(self, models, lr, weight_decay, grad_clip, seeds=None, batch_size=32):
-        G = len(models)
-        if G == 0:
-            raise _lib.MerError("FusionTopnGroupTrainer needs at least one model")
-        nets = [_topn_of(m) for m in models]
-        arch = _arch(nets[0])
-        for n in nets:
-            if _arch(n) != arch:
-                raise _lib.MerError(f"a group holds models of one architecture: {_arch(n)} != {arch}")
+    _ABI = "mer_fusion_topn_group"
+    _net = staticmethod(_topn_of)
+    _arch = staticmethod(_arch)
+
+    def _set_arch(self, arch):
         self.D, self.H, self.C1, self.C2 = arch
         self.M = len(self.D)
-        self.G, self.B = G, int(batch_size)
-        self.models = models
-        P = param_count(self.D, self.H, self.C1, self.C2)
-        params0 = [p for p in models[0].parameters() if p.requires_grad]
-        if not params0[0].is_cuda:
-            raise _lib.MerError("FusionTopnGroupTrainer needs the models on the GPU (there is no CPU path)")
-        dev = params0[0].device
-        if sum(p.numel() for p in params0) != P:
-            raise _lib.MerError("parameter count differs from the grouped kernels' layout")
-        self.P, self.dev = P, dev
-        self.flat = torch.empty((G, P), dtype=torch.float32, device=dev)
-        self.flat_grad = torch.zeros((G, P), dtype=torch.float32, device=dev)
-        self.m = torch.zeros((G, P), dtype=torch.float32, device=dev)
-        self.v = torch.zeros((G, P), dtype=torch.float32, device=dev)
-        self.step = torch.zeros(G, dtype=torch.int32, device=dev)
-        for g, mdl in enumerate(models):   # re-point every parameter (and its .grad) at row g of the group buffers
-            off = 0
-            for p in (q for q in mdl.parameters() if q.requires_grad):
-                k = p.numel()
-                self.flat[g, off:off + k].copy_(p.data.reshape(-1))
-                p.data = self.flat[g, off:off + k].view_as(p.data)
-                p.grad = self.flat_grad[g, off:off + k].view_as(p.data)
-                off += k
 
-        def per_model(x, name):
-            x = list(x) if isinstance(x, (list, tuple, np.ndarray)) else [x] * G
-            if len(x) != G:
-                raise _lib.MerError(f"{name}: {len(x)} values for {G} models")
-            return x
+    def _param_count(self):
+        return param_count(self.D, self.H, self.C1, self.C2)
 
-        self.lr = torch.tensor(per_model(lr, "lr"), dtype=torch.float32, device=dev)
-        self.wd = torch.tensor(per_model(weight_decay, "weight_decay"), dtype=torch.float32, device=dev)
-        self.clip = torch.tensor([float(c) for c in per_model(grad_clip, "grad_clip")], dtype=torch.float32, device=dev)
-        self.dropout = torch.tensor([float(n.encoder0.drop.p) for n in nets], dtype=torch.float32, device=dev)
-        seeds = per_model(seeds if seeds is not None else 0, "seeds")   # uint64 bits carried in an int64 tensor
-        self.seed = torch.from_numpy(np.array([int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds], dtype=np.uint64).view(np.int64)).to(dev)
-        self.cursor = torch.zeros(1, dtype=torch.int32, device=dev)
-        self._tables = None
-        self._cap = 0
-        self._graphs = {}
-        self._ws = None
+    @staticmethod
+    def _dropout_p(n):
+        return n.encoder0.drop.p
+
+    def _val_shape(self, S):
+        return (S, self.G, self.B, self.C2)
+
+    def _new_desc(self):
+        t = self._tables
+        d = _lib.FusionTopnGroup(G=self.G, B=self.B, n_steps=self._cap, M=self.M, H=self.H, C1=self.C1, C2=self.C2, emo=_p(t["emo"]),
+                                 val=_p(t["val"]) if self.C2 else None, out_val=_p(self.out_val) if self.C2 else None,
+                                 **self._common_fields())
+        for i in range(self.M):
+            d.D[i] = self.D[i]
+            d.feat[i] = _p(t["feats"][i])
+        return d
 
     # ---- data ----
     def set_tables(self, feats, emos, vals=None):
@@ -132,38 +106,3 @@ class FusionTopnGroupTrainer(FusionGroupTrainer):
             raise _lib.MerError("split tables: shapes do not match the models' input dims / each other")
         self._tables = dict(a=feats[0], feats=feats, emo=emo, val=val)   # "a": the table run() takes the row count from
         self._graphs = {}
-
-    def _reserve(self, S):
-        if S <= self._cap:
-            return
-        G, B, dev = self.G, self.B, self.dev
-        self._cap = S
-        self.index = torch.zeros((S, G, B), dtype=torch.int32, device=dev)
-        self.count = torch.zeros((S, G), dtype=torch.int32, device=dev)
-        self.out_loss = torch.zeros((S, G), dtype=torch.float32, device=dev)
-        self.out_emo = torch.zeros((S, G, B, self.C1), dtype=torch.float32, device=dev)
-        self.out_val = torch.zeros((S, G, B, self.C2), dtype=torch.float32, device=dev)
-        self._graphs = {}
-
-    def _desc(self):
-        t = self._tables
-        d = _lib.FusionTopnGroup(G=self.G, B=self.B, n_steps=self._cap, M=self.M, H=self.H, C1=self.C1, C2=self.C2, P=self.P,
-                                 params=_p(self.flat), grads=_p(self.flat_grad), adam_m=_p(self.m), adam_v=_p(self.v),
-                                 step=_p(self.step), lr=_p(self.lr), weight_decay=_p(self.wd), grad_clip=_p(self.clip),
-                                 dropout=_p(self.dropout), seed=_p(self.seed), beta1=0.9, beta2=0.999, eps=1e-8,
-                                 emo=_p(t["emo"]), val=_p(t["val"]) if self.C2 else None, n_rows=t["a"].shape[0],
-                                 index=_p(self.index), count=_p(self.count), cursor=_p(self.cursor),
-                                 out_loss=_p(self.out_loss), out_emo=_p(self.out_emo), out_val=_p(self.out_val) if self.C2 else None)
-        for i in range(self.M):
-            d.D[i] = self.D[i]
-            d.feat[i] = _p(t["feats"][i])
-        if self._ws is None:
-            nbytes = _lib.lib().mer_fusion_topn_group_workspace_bytes(ctypes.byref(d))
-            if nbytes < 0:
-                _lib.check(int(nbytes), "mer_fusion_topn_group_workspace_bytes")
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
-        d.workspace, d.workspace_bytes = _p(self._ws), self._ws.numel()
-        return d
-
-    def _launch(self, d, train):
-        _lib.check(_lib.lib().mer_fusion_topn_group_step(ctypes.byref(d), int(train), stream()), "mer_fusion_topn_group_step")

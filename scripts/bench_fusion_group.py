@@ -106,7 +106,7 @@ def launches(G, steps=10):
         calls = 0
         for f in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
             for row in csv.DictReader(open(f)):
-                if "fg_" in row["Name"]:
+                if "tg_" in row["Name"]:   # the group engine's kernels (csrc/fusion_topn_group.hip)
                     calls += int(row["Calls"])
     return calls / (steps + 1)   # + the one uncaptured warm-up step
 

@@ -1,4 +1,4 @@
-"""Grouped fusion training (csrc/fusion_group.hip, mertools_amd.fusion_group, main_release --parallel_folds / --num_trials) on the
+"""Grouped fusion training (the mer_fusion_group_* ABI of csrc/fusion_topn_group.hip, mertools_amd.fusion_group, main_release --parallel_folds / --num_trials) on the
 GPU: the reference's golden steps, bitwise equality with FusionGraphTrainer at dropout 0, group invariance (position, idle models,
 group size), the counter-based dropout masks, eval steps and the CLI against the default sequential path."""
 import argparse
@@ -153,7 +153,7 @@ def test_group_invariance_with_dropout(dev):
 
 
 def _np_mask(seed, step, site, rows, cols, p):
-    """The documented hash of csrc/fusion_group.hip, restated in numpy."""
+    """The documented hash of the mer_fusion_group_* ABI (csrc/fusion_topn_group.hip, shift 30), restated in numpy."""
     with np.errstate(over="ignore"):
         r = np.arange(rows, dtype=np.uint64)[:, None]
         c = np.arange(cols, dtype=np.uint64)[None, :]

@@ -95,7 +95,10 @@ def test_bad_shapes_fail_without_a_gpu(lib):
 
 
 def test_topn_group_kernels_use_no_scratch_memory(lib):
+    """No kernel of the group engine touches scratch.  fusion_topn_group.hip is the only translation unit with group kernels, so
+    this covers every launch of mer_fusion_topn_group_step and of mer_fusion_group_step (the 3-stream ABI on the same engine)."""
     from mertools_amd import build as B
+    assert "fusion_topn_group.hip" in B.SOURCES and "fusion_group.hip" not in B.SOURCES
     name, seen = None, 0
     for line in open(os.path.join(B.OBJ, "fusion_topn_group.hip.resources.txt")):
         m = re.search(r"Function Name: (\S+)", line)

@@ -83,7 +83,9 @@ def test_topn_group_matches_golden_reference(dev):
 def test_three_streams_bitwise_equal_the_merged_group(dev):
     """M = 3, C2 = 1, dropout 0: three models (different inits and lrs, one with grad_clip > 0), 20 steps, partial last batches:
     losses, emotion logits, valence outputs, final parameters, Adam moments and step counters are torch.equal to
-    FusionGroupTrainer's on the same flat parameters (the two parameter layouts coincide for three streams) and minibatches."""
+    FusionGroupTrainer's on the same flat parameters (the two parameter layouts coincide for three streams) and minibatches.
+    Both trainers run the one group engine, through two C ABIs: what this compares is the mer_fusion_group_* adapter's field
+    mapping (Da, Dt, Dv -> D[0..2], feat_a, feat_t, feat_v -> feat[0..2], M = 3) against a descriptor stated directly."""
     from mertools_amd.fusion_group import FusionGroupTrainer
     from mertools_amd.fusion_topn_group import FusionTopnGroupTrainer
     from mertools_amd.toolkit.models import get_models
@@ -180,7 +182,7 @@ def test_topn_group_invariance_with_dropout(dev, dims, C2):
 
 
 def _np_mask(seed, step, site, rows, cols, p):
-    """The documented hash of csrc/fusion_topn_group.hip, restated in numpy: ctr = step << 32 | site << 27 | row << 16 | col."""
+    """The documented hash of the mer_fusion_topn_group_* ABI (csrc/fusion_topn_group.hip, shift 27), restated in numpy: ctr = step << 32 | site << 27 | row << 16 | col."""
     with np.errstate(over="ignore"):
         r = np.arange(rows, dtype=np.uint64)[:, None]
         c = np.arange(cols, dtype=np.uint64)[None, :]

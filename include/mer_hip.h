@@ -391,6 +391,28 @@ int mer_fusion_topn_group_step(const mer_fusion_topn_group* desc, int train, mer
 int mer_fusion_topn_group_dropout_mask(uint64_t seed, int step, int site, int rows, int cols, float p, uint8_t* keep,
                                        mer_stream_t stream);
 
+/* ---- Low-rank Multimodal Fusion (csrc/lmf.hip; MERBench/toolkit/models/lmf.py:64-86), fp32, for m in {audio, video, text}:
+ *        P_m[r,b,o] = F_m[r,0,o] + sum_k h_m[b,k] F_m[r,k+1,o]        (the reference's appended column of ones, folded in)
+ *        out[b,o]   = sum_r w[r] P_a[r,b,o] P_v[r,b,o] P_t[r,b,o] + bias[o]
+ *      h_m [B,H]; F_m [R,H+1,O], the parameter's own layout; w [R]; bias [O].  1 <= H <= 1024, 1 <= O <= 512, 1 <= R <= 16,
+ *      1 <= B <= 2048; anything else, or a NULL required pointer, is a negative status with mer_last_error() naming the
+ *      function, decided before anything touches a GPU.
+ *      mer_lmf_fwd is ONE launch: writes out [B,O] and, unless proj is NULL, proj [3,R,B,O] = (P_a, P_v, P_t) for the backward.
+ *      Row b of out is computed from row b of h_* alone: the same bits at any B.
+ *      mer_lmf_bwd is ONE launch: from dout [B,O], the forward's inputs and proj it OVERWRITES dfa / dfv / dft [R,H+1,O],
+ *      dw [R], dbias [O] and those of dha / dhv / dht [B,H] that are not NULL (the others are bitwise unaffected).
+ *      No floating-point atomics: sums over b (factor, weight, bias gradients) and over (r, o) (dh) run in one fixed order,
+ *      so two calls on the same inputs give the same bits.  Neither call allocates, synchronises or reads device data on
+ *      the host (both may be captured into a HIP graph); mer_lmf_workspace_bytes is 0 for every valid shape (workspace
+ *      may be NULL) and negative for an invalid one. */
+int mer_lmf_fwd(const float* ha, const float* hv, const float* ht, const float* fa, const float* fv, const float* ft,
+                const float* w, const float* bias, int B, int H, int R, int O, float* proj, float* out, mer_stream_t stream);
+int mer_lmf_bwd(const float* dout, const float* ha, const float* hv, const float* ht, const float* fa, const float* fv,
+                const float* ft, const float* w, const float* proj, int B, int H, int R, int O, float* dha, float* dhv,
+                float* dht, float* dfa, float* dfv, float* dft, float* dw, float* dbias, void* workspace,
+                long long workspace_bytes, mer_stream_t stream);
+long long mer_lmf_workspace_bytes(int B, int H, int R, int O);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Encoder level                                                                              */
 /* ------------------------------------------------------------------------------------------ */

@@ -213,6 +213,9 @@ _PROTOS = {
     "mer_fusion_topn_group_workspace_bytes": (c_ll, [C.POINTER(FusionTopnGroup)]),
     "mer_fusion_topn_group_step": (c_int, [C.POINTER(FusionTopnGroup), c_int, c_void_p]),
     "mer_fusion_topn_group_dropout_mask": (c_int, [C.c_uint64, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
+    "mer_lmf_fwd": (c_int, [c_void_p] * 8 + [c_int] * 4 + [c_void_p, c_void_p, c_void_p]),
+    "mer_lmf_bwd": (c_int, [c_void_p] * 9 + [c_int] * 4 + [c_void_p] * 8 + [c_void_p, c_ll, c_void_p]),
+    "mer_lmf_workspace_bytes": (c_ll, [c_int, c_int, c_int, c_int]),
     "mer_hubert_create": (c_int, [C.POINTER(HubertConfig), C.POINTER(HubertWeights), C.POINTER(c_void_p)]),
     "mer_hubert_destroy": (None, [c_void_p]),
     "mer_hubert_out_frames": (c_int, [c_void_p, c_int]),

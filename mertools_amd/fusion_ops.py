@@ -120,6 +120,49 @@ class FuseFn(torch.autograd.Function):
         return dh, datt
 
 
+class LMFFuseFn(torch.autograd.Function):
+    """out[b,o] = sum_r w[r] P_a P_v P_t + bias[o],  P_m[r,b,o] = F_m[r,0,o] + sum_k h_m[b,k] F_m[r,k+1,o]  (lmf.py:73-85).
+    h_m [B,H], F_m [R,H+1,O], w [1,R], bias [1,O]; one launch forward (mer_lmf_fwd, which keeps P for the backward) and one
+    backward (mer_lmf_bwd)."""
+
+    @staticmethod
+    def forward(ctx, ha, hv, ht, fa, fv, ft, w, bias):
+        ha, hv, ht, fa, fv, ft, w, bias = (_c(t) for t in (ha, hv, ht, fa, fv, ft, w, bias))
+        if not (ha.dim() == 2 and fa.dim() == 3 and hv.shape == ht.shape == ha.shape and fv.shape == ft.shape == fa.shape
+                and fa.shape[1] == ha.shape[1] + 1 and w.numel() == fa.shape[0] and bias.numel() == fa.shape[2]):
+            raise _lib.MerError(f"lmf_fuse: shapes h {tuple(ha.shape)}/{tuple(hv.shape)}/{tuple(ht.shape)}, factors "
+                                f"{tuple(fa.shape)}/{tuple(fv.shape)}/{tuple(ft.shape)}, weights {tuple(w.shape)}, bias {tuple(bias.shape)}")
+        (B, H), (R, _, O) = ha.shape, fa.shape
+        proj = torch.empty((3, R, B, O), dtype=torch.float32, device=ha.device)
+        out = torch.empty((B, O), dtype=torch.float32, device=ha.device)
+        _lib.check(_lib.lib().mer_lmf_fwd(_p(ha), _p(hv), _p(ht), _p(fa), _p(fv), _p(ft), _p(w), _p(bias), B, H, R, O,
+                                          _p(proj), _p(out), stream()), "mer_lmf_fwd")
+        ctx.save_for_backward(ha, hv, ht, fa, fv, ft, w, proj)
+        ctx.shapes = (w.shape, bias.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        ha, hv, ht, fa, fv, ft, w, proj = ctx.saved_tensors
+        dout = _c(dout)
+        B, H = ha.shape
+        R, _, O = fa.shape
+        dh = [torch.empty_like(ha) if ctx.needs_input_grad[i] else None for i in range(3)]
+        dfa, dfv, dft = torch.empty_like(fa), torch.empty_like(fv), torch.empty_like(ft)
+        dw = torch.empty(ctx.shapes[0], dtype=torch.float32, device=dout.device)
+        dbias = torch.empty(ctx.shapes[1], dtype=torch.float32, device=dout.device)
+        _lib.check(_lib.lib().mer_lmf_bwd(_p(dout), _p(ha), _p(hv), _p(ht), _p(fa), _p(fv), _p(ft), _p(w), _p(proj), B, H, R, O,
+                                          _p(dh[0]), _p(dh[1]), _p(dh[2]), _p(dfa), _p(dfv), _p(dft), _p(dw),
+                                          _p(dbias), None, 0, stream()), "mer_lmf_bwd")
+        return dh[0], dh[1], dh[2], dfa, dfv, dft, dw, dbias
+
+
+def lmf_fuse(audio_h, video_h, text_h, audio_factor, video_factor, text_factor, fusion_weights, fusion_bias):
+    """Low-rank multimodal fusion of three [B,H] encoder outputs -> [B,O]; parameters in the reference module's layouts
+    (factors [R,H+1,O], fusion_weights [1,R], fusion_bias [1,O])."""
+    return LMFFuseFn.apply(audio_h, video_h, text_h, audio_factor, video_factor, text_factor, fusion_weights, fusion_bias)
+
+
 class DropoutFn(torch.autograd.Function):
     """Inverted dropout; the keep-mask comes from torch's RNG (so torch.manual_seed governs it), the arithmetic is HIP."""
 

@@ -103,7 +103,9 @@ typedef struct {
   int tile;     /* 0 = auto; 1 = 128x128; 2 = 128x64 (narrow N); 3 = 256x256 (8 waves, 1 workgroup/CU) */
   /* headmajor_T > 0: the 16-bit output is written head-major for attention instead of row-major:
    * element (row = b*T + t, col = which*64*H + h*64 + d) goes to c16[which][b][h][t][d] (contiguous [T,64] per head);
-   * needs M % T == 0, N % (64*H) == 0, c16_hi, no batching. */
+   * needs M % T == 0, N % (64*H) == 0, c16_hi, no batching — and the vector epilogue (only it scatters): ldc16 % 8 == 0 (it still
+   * takes part in the alignment check although head-major addressing does not use it), c16_hi / c16_lo 16-byte aligned, and, where
+   * given, c32 and residual 16-byte aligned with ldc32 % 4 == 0 and ldr % 4 == 0.  Anything else is refused with MER_ESHAPE. */
   int headmajor_T, headmajor_H;
   const void* w_mx;   /* passes == 4: packed MX-fp4 residual plane of W (mer_mx_pack), 16-byte aligned */
   /* optional pre-blocked copies of w_hi / w_lo (mer_w_block_pack): used instead of the row-major planes by the

@@ -220,6 +220,10 @@ extern "C" int mer_gemm16(const mer_gemm16_args* a, mer_stream_t stream) {
   if (a->c16_hi) vec = vec && (a->ldc16 % 8 == 0) && (((uintptr_t)a->c16_hi & 15) == 0);
   if (a->c16_lo) vec = vec && (((uintptr_t)a->c16_lo & 15) == 0);
   p.vec_ok = vec ? 1 : 0;
+  // the head-major scatter lives in the vector epilogue only: the scalar one would write row-major at row * ldc16 + col, outside the
+  // [which][b][h][t][64] planes
+  MER_REQUIRE(a->headmajor_T == 0 || vec, MER_ESHAPE,
+              "mer_gemm16: head-major output needs the vector epilogue: ldc16 %% 8 == 0, ldc32 / ldr %% 4 == 0 and 16-byte aligned c16_hi / c16_lo / c32 / residual");
   // fp32-only epilogue: whole-line residual loads / stores (4 columns per lane); N % 8 == 0 and 16-byte alignment are `vec`
   p.epi32 = (!g_gemm_generic_epi && vec && a->c32 && !a->c16_hi && !a->c16_lo && a->headmajor_T == 0 && (a->act == MER_ACT_NONE || a->act == MER_ACT_GELU) &&
              (!a->bias || ((((uintptr_t)a->bias) & 15) == 0 && a->bias_si % 4 == 0))) ? 1 : 0;   // its static bias is one 16-byte load per lane

@@ -1,7 +1,7 @@
 """Plain torch fp64 references of the op-level kernels (include/mer_hip.h), one function per op.
 
-Nothing here touches the GPU or imports the library: these are the yardsticks of tests/test_attention_matrix_gpu.py and
-tests/test_rowops_gpu.py, and tests/test_op_refs_cpu.py pins them against torch's own operators.  Layouts are the ABI's:
+Nothing here touches the GPU or imports the library: these are the yardsticks of tests/test_attention_matrix_gpu.py,
+tests/test_gemm_matrix_gpu.py and tests/test_rowops_gpu.py, and tests/test_op_refs_cpu.py pins them against torch's own operators.  Layouts are the ABI's:
 qkv is [B*T, 3*H*64] with the q | k | v column blocks, head h at columns 64 h .. 64 h + 63 of its block.
 """
 import torch
@@ -95,6 +95,12 @@ def act_ref(x, act):
         return x
     if act == "gelu":
         return F.gelu(x)
+    if act == "quick_gelu":
+        return x * torch.sigmoid(1.702 * x)
+    if act in ("gelu_tanh", "gelu_new"):
+        return F.gelu(x, approximate="tanh")
+    if act == "relu":
+        return F.relu(x)
     raise ValueError(act)
 
 
@@ -189,3 +195,91 @@ def is_canary16(t):
 
 
 CANARY32 = -1.2345678e30
+
+
+def is_canary32(t):
+    return bool((t == CANARY32).all())
+
+
+# --------------------------------------------------------------------------------------------------------------------- gemm16
+U16 = {"f16": 2.0 ** -11, "bf16": 2.0 ** -8}          # unit roundoff of one 16-bit plane (round to nearest)
+U_PAIR = {"f16": 2.0 ** -21, "bf16": U2}              # ... and of a hi + lo pair
+GEMM_TOL = 2e-5                                       # the project's max-norm relative bound on an fp32 GEMM output (tests/test_ops_gpu.py)
+GEMM_TERMS = {1: ("hh",), 2: ("hh", "hl"), 3: ("hh", "hl", "lh"), 6: ("hh", "lh")}    # passes -> plane products, (A plane)(W plane)
+
+
+def gemm16_terms_ref(a_hi, a_lo, w_hi, w_lo, terms):
+    """fp64 sum of the named plane products: "hl" = a_hi . w_lo^T and so on ("ll" exists only to model a mis-paired pass)."""
+    pa, pw = {"h": a_hi, "l": a_lo}, {"h": w_hi, "l": w_lo}
+    return sum(pa[t[0]].double() @ pw[t[1]].double().T for t in terms)
+
+
+def gemm16_planes_ref(a_hi, a_lo, w_hi, w_lo, passes):
+    """What mer_gemm16 accumulates for `passes`, in fp64 on the ROUNDED planes: 1 = hh, 2 = hh + a_hi.w_lo, 3 = hh + a_hi.w_lo +
+    a_lo.w_hi, 6 = hh + a_lo.w_hi.  The planes are the inputs, so the reference carries no input rounding and one tolerance serves
+    both 16-bit types."""
+    return gemm16_terms_ref(a_hi, a_lo, w_hi, w_lo, GEMM_TERMS[passes])
+
+
+def gemm_epilogue_ref(z, bias=None, act=None, residual=None, table=None, seg_rows=0):
+    """fp64 epilogue of mer_gemm16 on pre-activations z [M, N]: + bias[n] (or + table[m // seg_rows, n]), act, + residual."""
+    z = z.double()
+    if table is not None:
+        assert bias is None and seg_rows > 0
+        z = z + table.double().repeat_interleave(seg_rows, 0)[:z.shape[0], :z.shape[1]]
+    elif bias is not None:
+        z = z + bias.double()
+    z = act_ref(z, act)
+    return z if residual is None else z + residual.double()
+
+
+def act_model32(x, act):
+    """The activation formulas of csrc/common.h restated in torch fp32 (exact exp / division where the kernel uses v_exp_f32 /
+    v_rcp_f32): what fp32 arithmetic alone costs against act_ref.  Only the two formulas whose bound is derived from it."""
+    x = x.float()
+    if act == "quick_gelu":
+        return x * (1.0 / (1.0 + torch.exp(-1.702 * x)))
+    if act in ("gelu_tanh", "gelu_new"):
+        u = 0.7978845608028654 * (x + 0.044715 * x * x * x)
+        return 0.5 * x * (2.0 - 2.0 / (torch.exp(2.0 * u) + 1.0))
+    raise ValueError(act)
+
+
+def act_bound(pre, act, residual=None):
+    """(bound, model) for an fp32 output after `act`: 2e-5 for none / gelu / relu; max(2e-5, 2 x model) for quick_gelu / gelu_tanh,
+    model = max-norm relative error of act_model32 on these very pre-activations against fp64 (never the kernel's output)."""
+    if act not in ("quick_gelu", "gelu_tanh", "gelu_new"):
+        return GEMM_TOL, 0.0
+    ref = act_ref(pre.double(), act)
+    got = act_model32(pre, act).double()
+    if residual is not None:
+        ref, got = ref + residual.double(), got + residual.double()
+    model = (got - ref).abs().max().item() / max(ref.abs().max().item(), 1e-30)
+    return max(GEMM_TOL, 2.0 * model), model
+
+
+def indep_planes(M, N, K, dtype, seed):
+    """Input family "indep": four INDEPENDENT random 16-bit planes, a_hi ~ N(0, 1), a_lo ~ 0.5 N(0, 1), w_hi ~ 0.05 N(0, 1), w_lo ~
+    0.025 N(0, 1).  The lo planes are nobody's residual — the kernel cannot tell — and every product term is of order 1 next to hh,
+    so a dropped or mis-paired pass moves the result by tens of percent instead of 2^-11."""
+    t16 = T16[dtype]
+    return (rand((M, K), seed).to(t16), rand((M, K), seed + 1, 0.5).to(t16),
+            rand((N, K), seed + 2, 0.05).to(t16), rand((N, K), seed + 3, 0.025).to(t16))
+
+
+def split_planes(x, dtype):
+    """Input family "split": the true hi / lo split of fp32 data (hi = rn(x), lo = rn(x - hi))."""
+    t16 = T16[dtype]
+    hi = x.float().to(t16)
+    return hi, (x.float() - hi.float()).to(t16)
+
+
+def round16(x, dtype):
+    return x.float().to(T16[dtype])
+
+
+def auto_tile(M, N, passes):
+    """The tile == 0 rule of mer_gemm16 (csrc/gemm16.hip) for a non-MX launch: 2 = 128x64, 1 = 128x128, 3 = 256x256."""
+    t256 = -(-M // 256) * -(-N // 256)
+    few_narrow = t256 <= 96 and N <= 1024 and passes != 4
+    return 2 if N <= 64 else (3 if (M >= 1024 and N >= 192 and not few_narrow) else 1)

@@ -116,3 +116,73 @@ def test_row_refs():
     assert torch.equal(R.add_pos_ref(x.view(15, 8), x[0]), x.view(15, 8) + x[0].repeat(5, 1))
     g = R.swiglu_ref(torch.tensor([[-100.0, 30.0, 2.0, -3.0]]), 2)
     assert g[0, 0].item() == pytest.approx(-100.0 / (1 + torch.exp(torch.tensor(100.0, dtype=torch.float64)).item()) * 2.0) and g[0, 1].item() == pytest.approx(-90.0)
+
+
+# ------------------------------------------------------------------------------------------------------------------ gemm16
+GEMM_SHAPES = [(129, 136, 8), (129, 136, 160), (257, 264, 72), (1, 8, 8), (129, 75, 40)]
+
+
+@pytest.mark.parametrize("dtype", ["f16", "bf16"])
+def test_gemm16_planes_ref_reproduces_a_true_split(dtype):
+    """On a true hi / lo split the 3-pass plane sum is the fp32-grade product: a.w up to the dropped a_lo.w_lo term and the
+    rounding of the lo planes — 1e-6 for f16 (2^-22 per operand), U2-grade for bf16 (2^-16 per operand, two operands, averaged
+    down by the sum over k: bounded by 4 U2)."""
+    M, N, K = 129, 136, 160
+    a, w = R.rand((M, K), 21), R.rand((N, K), 22, 0.05)
+    ah, al = R.split_planes(a, dtype)
+    wh, wl = R.split_planes(w, dtype)
+    want = a.double() @ w.double().T
+    got = R.gemm16_planes_ref(ah, al, wh, wl, 3)
+    e = (got - want).abs().max().item() / want.abs().max().item()
+    assert e <= (1e-6 if dtype == "f16" else 4 * R.U2), e
+    assert e > 0.0
+    for passes, terms in R.GEMM_TERMS.items():                                   # the table in the docstring, term by term
+        z = ah.double() @ wh.double().T
+        if "hl" in terms:
+            z = z + ah.double() @ wl.double().T
+        if "lh" in terms:
+            z = z + al.double() @ wh.double().T
+        assert torch.equal(R.gemm16_planes_ref(ah, al, wh, wl, passes), z)
+
+
+@pytest.mark.parametrize("dtype", ["f16", "bf16"])
+@pytest.mark.parametrize("M,N,K", GEMM_SHAPES)
+def test_indep_planes_discriminate_every_pass_set(dtype, M, N, K):
+    """The "indep" family must keep telling the pass sets apart: for every passes value, every OTHER set of lo terms (a dropped or
+    an extra pass) and a_lo.w_lo in place of either lo term move the fp64 reference by at least 1000 x the GPU tolerance (max-norm
+    relative) — while plain fp32 arithmetic on the same planes stays far inside that tolerance."""
+    P = R.indep_planes(M, N, K, dtype, 500 + M + N + K)
+    for passes, terms in R.GEMM_TERMS.items():
+        ref = R.gemm16_planes_ref(*P, passes)
+        scale = ref.abs().max().item()
+        wrong = [t for p, t in R.GEMM_TERMS.items() if p != passes]
+        wrong += [tuple("ll" if t == x else t for t in terms) for x in terms if x != "hh"]
+        for alt in wrong:
+            moved = (R.gemm16_terms_ref(*P, alt) - ref).abs().max().item() / scale
+            assert moved >= 1000 * R.GEMM_TOL, (passes, alt, moved)
+        f32 = sum({"h": P[0], "l": P[1]}[t[0]].float() @ {"h": P[2], "l": P[3]}[t[1]].float().T for t in terms)
+        assert (f32.double() - ref).abs().max().item() / scale <= 1e-6, passes
+
+
+def test_gemm_epilogue_ref_and_act_model():
+    z, bias, res = R.rand((7, 5), 31, 3.0), R.rand((5,), 32), R.rand((7, 5), 33)
+    tab = R.rand((3, 8), 34)                                                     # a table wider than N: only its first N columns count
+    want = F.gelu(z.double() + bias.double(), approximate="tanh") + res.double()
+    assert torch.equal(R.gemm_epilogue_ref(z, bias=bias, act="gelu_tanh", residual=res), want)
+    rows = torch.tensor([0, 0, 0, 1, 1, 1, 2])
+    assert torch.equal(R.gemm_epilogue_ref(z, table=tab, seg_rows=3, act="relu"), F.relu(z.double() + tab.double()[rows, :5]))
+    assert torch.equal(R.gemm_epilogue_ref(z, act="quick_gelu"), z.double() * torch.sigmoid(1.702 * z.double()))
+    x = R.rand((4000,), 35, 4.0)
+    for act in ("quick_gelu", "gelu_tanh"):
+        bound, model = R.act_bound(x, act)
+        assert 0.0 < model < 1e-6 and bound == R.GEMM_TOL, (act, model)             # fp32 arithmetic alone is far inside 2e-5
+    assert R.act_bound(x, "gelu") == (R.GEMM_TOL, 0.0)
+
+
+def test_auto_tile_rule_at_its_edges():
+    assert [R.auto_tile(2000, n, 1) for n in (8, 64, 65)] == [2, 2, 1]
+    assert R.auto_tile(1023, 1280, 1) == 1 and R.auto_tile(1024, 1280, 1) == 3
+    assert R.auto_tile(1024, 191, 1) == 1 and R.auto_tile(1024, 192, 1) == 1    # 4 tiles of 256 x 256, N <= 1024: few_narrow
+    assert R.auto_tile(1024, 1024, 1) == 1 and R.auto_tile(1024, 1032, 1) == 3  # few_narrow on / off at N = 1024
+    assert R.auto_tile(6400, 1024, 1) == 3 and R.auto_tile(6144, 1024, 1) == 1  # 100 / 96 tiles of 256 x 256
+    assert R.auto_tile(1024, 191, 4) == 1 and R.auto_tile(1024, 192, 4) == 3    # passes 4 is never few_narrow: the N >= 192 edge

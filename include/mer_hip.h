@@ -296,12 +296,15 @@ int mer_colsum(const float* x, int M, int N, long long ldx, float* out, int accu
 int mer_dropout(const float* x, const uint8_t* keep, float scale, float* out, long long n, mer_stream_t stream);
 /* fused[b,j] = sum_e h[b,e*H+j]*att[b,e]  (h = cat of the E modality encoders' outputs, att NOT softmaxed) */
 int mer_fuse_fwd(const float* h, const float* att, float* out, int B, int H, int E, mer_stream_t stream);
+/* dh[b,e*H+j] = dout[b,j]*att[b,e], datt[b,e] = sum_j dout[b,j]*h[b,e*H+j].  Requires B > 0, H > 0 and E > 0
+ * (MER_EINVAL otherwise, before any launch). */
 int mer_fuse_bwd(const float* dout, const float* h, const float* att, float* dh, float* datt, int B, int H, int E,
                  mer_stream_t stream);
 /* CELoss = NLL(log_softmax(logits,1), target, 'sum')/B; probs [B,C] and row_scratch [B] are device scratch
  * kept for the backward; loss is a device scalar. */
 int mer_ce_loss(const float* logits, const int64_t* target, int B, int C, float* probs, float* row_scratch, float* loss,
                 mer_stream_t stream);
+/* dlogits = gout * (probs - onehot(target)) / B.  Requires B > 0 and C > 0 (MER_EINVAL otherwise, before any launch). */
 int mer_ce_loss_bwd(const float* probs, const int64_t* target, const float* gout, float* dlogits, int B, int C,
                     mer_stream_t stream);
 /* MSELoss = sum((pred-target)^2)/B on [B] vectors */

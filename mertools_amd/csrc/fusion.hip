@@ -27,13 +27,15 @@ __global__ void dropout_kernel(const float* x, const uint8_t* keep, float scale,
 }
 
 // fused[b,j] = sum_e h[b, e*H + j] * att[b,e]   (torch.matmul([B,H,3],[B,3,1]) of attention.py:48-50)
+// Grid-stride: g1() caps the grid at 4096 blocks, so B*H may exceed the number of threads launched.
 __global__ void fuse_fwd_kernel(const float* h, const float* att, float* out, int B, int H, int E) {
-  const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-  if (i >= (long long)B * H) return;
-  const int b = (int)(i / H), j = (int)(i % H);
-  float s = 0.f;
-  for (int e = 0; e < E; ++e) s = fmaf(h[(long long)b * E * H + e * H + j], att[b * E + e], s);
-  out[i] = s;
+  const long long n = (long long)B * H;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const int b = (int)(i / H), j = (int)(i % H);
+    float s = 0.f;
+    for (int e = 0; e < E; ++e) s = fmaf(h[(long long)b * E * H + e * H + j], att[b * E + e], s);
+    out[i] = s;
+  }
 }
 
 // dh[b,e*H+j] = dout[b,j]*att[b,e];  datt[b,e] = sum_j dout[b,j]*h[b,e*H+j].  One wave per (b,e).
@@ -161,7 +163,7 @@ extern "C" int mer_fuse_fwd(const float* h, const float* att, float* out, int B,
 }
 extern "C" int mer_fuse_bwd(const float* dout, const float* h, const float* att, float* dh, float* datt, int B, int H, int E,
                             mer_stream_t stream) {
-  MER_REQUIRE(dout && h && att && dh && datt && B > 0, MER_EINVAL, "mer_fuse_bwd: bad args");
+  MER_REQUIRE(dout && h && att && dh && datt && B > 0 && H > 0 && E > 0, MER_EINVAL, "mer_fuse_bwd: bad args");
   fuse_bwd_kernel<<<B * E, 64, 0, (hipStream_t)stream>>>(dout, h, att, dh, datt, B, H, E);
   return check_launch("fuse_bwd");
 }
@@ -175,7 +177,7 @@ extern "C" int mer_ce_loss(const float* logits, const int64_t* target, int B, in
 }
 extern "C" int mer_ce_loss_bwd(const float* probs, const int64_t* target, const float* gout, float* dlogits, int B, int C,
                                mer_stream_t stream) {
-  MER_REQUIRE(probs && target && gout && dlogits && B > 0, MER_EINVAL, "mer_ce_loss_bwd: bad args");
+  MER_REQUIRE(probs && target && gout && dlogits && B > 0 && C > 0, MER_EINVAL, "mer_ce_loss_bwd: bad args");
   ce_bwd_kernel<<<(unsigned)cdiv((long long)B * C, 256), 256, 0, (hipStream_t)stream>>>(probs, target, gout, dlogits, B, C);
   return check_launch("ce_loss_bwd");
 }

@@ -108,3 +108,16 @@ def test_hot_kernels_use_no_scratch_memory():
                 fallback = "Li256ELi256ELi32ELi2ELi4ELi2ELi2ELb0E" in name
                 assert int(m.group(1)) <= (64 if fallback else 0), f"{name} uses {m.group(1)} bytes/lane of scratch ({os.path.basename(f)})"
     assert seen >= 20, seen
+
+
+def test_fuse_bwd_and_ce_loss_bwd_refuse_empty_shapes(lib):
+    """include/mer_hip.h: mer_fuse_bwd needs B, H, E > 0 (its kernel divides the block index by E), mer_ce_loss_bwd needs B, C > 0.
+    Both are host checks that return MER_EINVAL before any launch: the pointers below are never dereferenced."""
+    buf = (ctypes.c_float * 16)()
+    p = ctypes.addressof(buf)
+    for B, H, E in ((2, 0, 3), (2, 4, 0), (2, -1, 3), (2, 4, -2), (0, 4, 3)):
+        assert lib.mer_fuse_bwd(p, p, p, p, p, B, H, E, None) == -1, (B, H, E)
+        assert b"mer_fuse_bwd" in lib.mer_last_error()
+    for B, Cn in ((2, 0), (2, -3), (0, 6)):
+        assert lib.mer_ce_loss_bwd(p, p, p, p, B, Cn, None) == -1, (B, Cn)
+        assert b"mer_ce_loss_bwd" in lib.mer_last_error()

@@ -140,29 +140,28 @@ def test_graph_trainer_matches_reference(dev, use_graph):
 # ---- frame-level fusion: LSTMEncoder on the HIP LSTM kernels ----
 @pytest.mark.parametrize("B,T,D,H", [(5, 7, 24, 16), (32, 40, 768, 128), (3, 130, 100, 256)])
 def test_lstm_last_matches_torch_lstm(dev, B, T, D, H):
-    """mer_lstm_fwd / mer_lstm_bwd + the GEMMs around them against torch.nn.LSTM (the reference's own op) on the CPU:
-    final hidden state and the gradients of every parameter and of the input."""
+    """mer_lstm_fwd / mer_lstm_bwd + the GEMMs around them against torch.nn.LSTM(...).double() (the reference's own op, in fp64) on
+    the CPU: final hidden state and the gradients of every parameter and of the input (tests/op_refs.py: lstm_ref)."""
     import torch.nn as nn
+    import op_refs
     from mertools_amd.fusion_ops import lstm_last
     torch.manual_seed(0)
-    ref = nn.LSTM(D, H, num_layers=1, batch_first=True)
+    init = nn.LSTM(D, H, num_layers=1, batch_first=True)
     x = torch.randn(B, T, D)
     x[: B // 2, : T // 3] = 0.0                        # front padding, as func_mapping_feature produces
-    xr = x.clone().requires_grad_(True)
-    _, (hn, _) = ref(xr)
     wgt = torch.randn(B, H)
-    (hn[0] * wgt).sum().backward()
+    hn, grads = op_refs.lstm_ref(x, init.state_dict(), wgt)
     dev_rnn = nn.LSTM(D, H, num_layers=1, batch_first=True)
-    dev_rnn.load_state_dict(ref.state_dict())
+    dev_rnn.load_state_dict(init.state_dict())
     dev_rnn = dev_rnn.to(dev)
     xd = x.clone().to(dev).requires_grad_(True)
     h = lstm_last(xd, dev_rnn)
     (h * wgt.to(dev)).sum().backward()
     torch.cuda.synchronize()
-    assert_close(h.detach().cpu(), hn[0].detach(), 2e-5, "lstm h_T")
-    assert_close(xd.grad.cpu(), xr.grad, 2e-4, "lstm dX")
+    assert_close(h.detach().cpu(), hn, 2e-5, "lstm h_T")
+    assert_close(xd.grad.cpu(), grads["x"], 2e-4, "lstm dX")
     for name in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"):
-        assert_close(getattr(dev_rnn, name).grad.cpu(), getattr(ref, name).grad, 2e-4, f"lstm d{name}")
+        assert_close(getattr(dev_rnn, name).grad.cpu(), grads[name], 2e-4, f"lstm d{name}")
 
 
 def test_attention_model_frame_level_matches_reference(dev):

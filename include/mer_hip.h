@@ -456,9 +456,16 @@ typedef struct {
   int gated_rel_pos;  /* 1: WavLM — every layer carries gru_* and the forward call must be given the position-bias table */
   int ffn_swiglu;     /* 1: DINOv2-giant SwiGLU feed-forward (HF:dinov2/modeling_dinov2.py Dinov2SwiGLUFFN): w1 = weights_in [2*ffn, D],
                        * h = silu(y[:, :ffn]) * y[:, ffn:], w2 = weights_out [D, ffn]; `ffn` is the post-gate width, `act` is ignored */
-  int mx_skip;        /* passes == 4 / 5: GEMMs that run WITHOUT the weight-residual correction (plain one-pass f16) because
-                       * their rounding error does not reach the saved features (tests/studies/mx_selective.py):
-                       * bit 0 = the Q and K projections (their error only perturbs softmax logits), bit 1 = FFN fc1, bit 2 = FFN fc2 */
+  int mx_skip;        /* GEMMs that run WITHOUT the weight-residual correction (plain one-pass f16) because their rounding error
+                       * does not reach the saved features (tests/studies/mx_selective.py): bit 0 = the Q and K projections (their
+                       * error only perturbs softmax logits), read under passes == 4 / 5 / 6; bit 1 = FFN fc1 and bit 2 = FFN fc2,
+                       * read under passes == 4 / 5 only.  Every other pass code ignores the field.
+                       * How bit 0 is carried out: passes == 4 with an MX plane on the fused weight and 2 * hidden % 256 == 0 — the
+                       * QKV GEMM is split into a one-pass Q | K GEMM and a passes == 4 V GEMM on rows [2 * hidden, 3 * hidden) of every
+                       * plane (tile 2 * hidden / 256 of the MX and pre-blocked planes); without an MX plane (bf16, hidden % 128 != 0) or
+                       * with 2 * hidden % 256 != 0 the fused GEMM stays whole and corrected.  passes == 5 AND passes == 6: the fused
+                       * QKV table is built with n_first = 2 * hidden (mer_seq_bias) — bit 0 is the one bit that passes == 6 honours;
+                       * bits 1 / 2 are read under passes == 4 / 5 only (a passes == 6 FFN always carries its table). */
   int attn_f32;       /* passes == 6: 1 = attention on fp32 q | k | v (mer_attention_f32: the QKV GEMM writes fp32) as passes == 3 always does;
                        * 0 = the 16-bit attention kernels */
 } mer_tf_config;
@@ -477,7 +484,17 @@ typedef struct {
   int feat_proj_layer_norm;
   int pos_k, pos_groups;
   int stable_layer_norm;    /* 1: HubertEncoderStableLayerNorm (large) */
-  int conv_passes;          /* GEMM passes in the conv stack + projection + positional conv: 1 .. 5 (as mer_tf_config.passes) */
+  int conv_passes;          /* GEMM passes in the conv stack + projection + positional conv: 1 .. 5 (as mer_tf_config.passes).
+                             * Conv GEMMs (conv1 ..): conv_passes as given; under 5 one sequence = the output frames of one clip at
+                             * that layer (valid_rows = its valid frame count there in a ragged batch).
+                             * Feature projection: its weight planes are those of conv_passes.  It runs with the per-sequence table
+                             * (one sequence = a clip's frames, valid_rows = its valid frames) when conv_passes == 5, and also when
+                             * feat_proj_layer_norm is set and tf.passes is 5 / 6 (behind that LayerNorm all rows are of one size);
+                             * the table then rides on two MFMA passes, as mer_tf_config.passes == 6, where the conv stack carries
+                             * the projection's input as hi + lo planes (conv_passes == 3) and on one pass, as 5, otherwise.
+                             * Without the table it runs conv_passes as given.
+                             * Positional conv: a batched GEMM over (clip, group) that neither the MX kernel nor the table covers:
+                             * conv_passes 4 / 5 run it as 2, every other code as given. */
   int pos_layers;           /* 0: HuBERT / wav2vec2 — one weight-normed conv, x + GELU(conv(x));
                              * n >= 1: data2vec-audio (HF:data2vec/modeling_data2vec_audio.py Data2VecAudioPositionalConvEmbedding) —
                              * n x [grouped conv (kernel pos_k, padding pos_k/2) -> LayerNorm without affine (eps 1e-5) -> GELU],
@@ -560,12 +577,23 @@ int mer_vit_create(const mer_vit_config* cfg, const mer_vit_weights* w, mer_vit*
 void mer_vit_destroy(mer_vit* h);
 long long mer_vit_workspace_bytes(const mer_vit* h, int N);
 /* pixels: device fp32 [N,3,S,S].  image_features fp32 [N, proj_dim] (may be NULL);
- * pooled fp32 [nseg, proj_dim] = mean of image_features rows per segment (may be NULL). */
+ * pooled fp32 [nseg, proj_dim] = mean of image_features rows per segment (may be NULL).
+ * CLS-only last block: CLIP features (variant 0) read the [CLS] row of the last block alone, so when no token states are asked for
+ * (tokens_out == NULL below), no layer carries attn_bias, the blocks run 16-bit attention (passes != 3, not passes == 6 with attn_f32)
+ * and 1 + P <= 584, the LAST block computes K | V for every token — one GEMM on rows [hidden, 3 * hidden) of the fused QKV weight,
+ * n_first = hidden under mx_skip bit 0 with passes 5 / 6 — but Q (a GEMM over the N [CLS] rows, row stride (1 + P) * hidden, on the
+ * row-major hi / lo planes alone: passes == 4 runs two passes there), mer_attention_cls, the output projection (residual = the [CLS]
+ * rows of the stream), the LayerNorm and the FFN for the N [CLS] rows only; under passes 5 / 6 every [CLS] row is its own sequence
+ * (seg_rows = 1).  The MX and pre-blocked planes are stored per 256-row tile, so the K | V GEMM reads them only when
+ * hidden % 256 == 0; otherwise it runs on the row-major planes and passes == 4 degrades to two passes.  The features of this path
+ * and of the full path (mer_vit_forward_tokens with tokens_out) agree to the preset's parity bar, not bit for bit
+ * (mer_attention_cls against the tiled kernel). */
 int mer_vit_forward(const mer_vit* h, const float* pixels, int N, void* workspace, long long workspace_bytes,
                     float* image_features, const int* seg_start, const int* seg_len, int nseg, float* pooled,
                     mer_stream_t stream);
 /* Same, and additionally copies the last residual stream [N, 1+P, D] (the last entry of HF's `hidden_states`) to
- * `tokens_out` when it is not NULL — what the drop-in `model(..., output_hidden_states=True).hidden_states[-1]` returns. */
+ * `tokens_out` when it is not NULL — what the drop-in `model(..., output_hidden_states=True).hidden_states[-1]` returns;
+ * a non-NULL tokens_out switches the CLS-only last block off (every block runs for every token). */
 int mer_vit_forward_tokens(const mer_vit* h, const float* pixels, int N, void* workspace, long long workspace_bytes,
                            float* image_features, const int* seg_start, const int* seg_len, int nseg, float* pooled,
                            float* tokens_out, mer_stream_t stream);

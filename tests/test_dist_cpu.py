@@ -68,15 +68,20 @@ class _Enc:
     def __init__(self, din, dout, seed):
         self.w = torch.randn(din, dout, generator=torch.Generator().manual_seed(seed)) / din ** 0.5
 
+    def proj(self, x):
+        """x @ w one row at a time: a row's bits must not depend on how many rows share the call (a CPU GEMM's blocking does on
+        some hosts), or a rank's 6-row shard could not equal the same rows of the single process's 11."""
+        return torch.stack([r @ self.w for r in x])
+
 
 class _A(_Enc):
     def extract_utterance(self, x):
-        return x[:, :self.w.shape[0]].float() @ self.w
+        return self.proj(x[:, :self.w.shape[0]].float())
 
 
 class _V(_Enc):
     def extract_utterance(self, x, frames_per_clip):
-        f = x.reshape(x.shape[0], -1)[:, :self.w.shape[0]].float() @ self.w
+        f = self.proj(x.reshape(x.shape[0], -1)[:, :self.w.shape[0]].float())
         out, r = [], 0
         for n in frames_per_clip:
             out.append(f[r:r + n].mean(0))
@@ -86,7 +91,7 @@ class _V(_Enc):
 
 class _T(_Enc):
     def extract_utterance(self, ids, lengths, start, end):
-        return (ids.float() / 1000.0)[:, :self.w.shape[0]] @ self.w
+        return self.proj((ids.float() / 1000.0)[:, :self.w.shape[0]])
 
 
 class _Trainer:

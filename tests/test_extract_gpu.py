@@ -48,7 +48,7 @@ def test_audio_extract_files(dev, tmp_path, level, precision):
         p = str(tmp_path / f"clip{i}.wav")
         _write_wav(p, rng.randn(L) * 0.1)
         files.append(p)
-    audio.MAXLEN = 10000
+    old_maxlen, audio.MAXLEN = audio.MAXLEN, 10000
     save_dir = str(tmp_path / f"feat-{level[:3]}")
     old = audio.split_into_batch.__defaults__
     audio.split_into_batch.__defaults__ = (10000,)
@@ -75,6 +75,7 @@ def test_audio_extract_files(dev, tmp_path, level, precision):
         print(f"audio driver [{precision} -> runs {model.precision}, {level}]: worst clip {worst:.2e} vs the oracle; self-check {getattr(model, 'self_check_result', None)}")
     finally:
         audio.split_into_batch.__defaults__ = old
+        audio.MAXLEN = old_maxlen      # (left at 10000 it broke tests/test_round6_cpu.py whenever both ran in one process)
 
 
 @pytest.mark.parametrize("level", ["UTTERANCE", "FRAME"])

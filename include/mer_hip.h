@@ -128,11 +128,26 @@ int mer_gemm16(const mer_gemm16_args* args, mer_stream_t stream);
  * (tests/studies/mean_correction.py) — i.e. it is a bias, one row per sequence.  Computed
  * for the ceil(M / seg_rows) sequences of seg_rows consecutive rows of the A plane (rows addressed like mer_gemm16's A operand).  The
  * sample of a sequence is rows h, h + s, h + 2 s, ... below its valid length (valid_rows[s], or seg_rows), s the largest power of two
- * that leaves at least 16 samples, h = s / 2; sums are exact 64-bit fixed-point integers, one owner per element (no atomics): the row
- * of a sequence depends on that sequence alone, bit for bit — whatever else is in the batch.  The one-pass GEMM that follows takes the
- * table through mer_gemm16_args.bias / bias_seg_rows / bias_ld.  Columns below n_first (a multiple of 16) get the plain bias (the
- * Q | K columns of a fused QKV weight need no correction).  scratch: device, mer_seq_bias_scratch_bytes(nseq, K) bytes, 16-byte
- * aligned (the 16-bit mean plane); table: device fp32 [nseq, ldt].  Two small launches on `stream`. */
+ * that leaves at least 16 samples (the largest with 16 s <= seg_rows; 1 below 16 rows, where every row is a sample), h = s / 2.  The
+ * valid length of sequence q is min(valid_rows[q], seg_rows, M - q * seg_rows): a valid_rows entry above seg_rows is clamped, the last
+ * sequence of the plane may be partial, and only sampled rows below that length are read.  A sequence has at most 32 samples (reached
+ * first at seg_rows = 127; a seg_rows that would need more is refused with MER_EUNSUPPORTED — none does).
+ * The mean: every sample is clamped to +-131000 and rounded to the nearest multiple of 2^-14 (ties to even); these fixed-point values are
+ * summed as 64-bit integers — exactly, in any order — and the sum times 1 / (samples * 2^14), in fp64, is rounded to fp32 and then to
+ * the 16-bit type (both to nearest even).  So for finite inputs within the clamp (every f16 value is)
+ *     |mean16 - mean of the samples| <= 2^-15 + one rounding to the 16-bit type
+ * and the mean plane is NOT the exactly rounded mean: inputs below 2^-15 in magnitude vanish from it.  Non-finite inputs do not
+ * propagate: +inf counts as 131000, -inf and NaN as -131000.  A sequence without a sample (valid length <= h) has mean 0: its table
+ * row is the plain bias.  One owner per element (no atomics): the row of a sequence depends on that sequence alone, bit for bit —
+ * whatever else is in the batch, wherever it stands in it.  The table product runs on the MFMA over the 16-bit mean plane, fp32
+ * accumulation, K split over 16 partial sums added in a fixed tree.  The one-pass GEMM that follows takes the
+ * table through mer_gemm16_args.bias / bias_seg_rows / bias_ld.  Columns below n_first (a multiple of 16, MER_EINVAL otherwise; it may
+ * exceed N) get the plain bias, bit for bit — 0 with bias == NULL — (the Q | K columns of a fused QKV weight need no correction).
+ * Requirements: K, lda, ldw and a_batch_stride multiples of 8, a / w_lo / scratch 16-byte aligned, ldt >= N (MER_ESHAPE otherwise);
+ * dtype f16 or bf16 (MER_EINVAL); at most 65535 sequences (MER_EUNSUPPORTED).  A refused call launches nothing.  Columns K .. lda of A,
+ * K .. ldw of w_lo and N .. ldt of the table are never touched.  scratch: device, mer_seq_bias_scratch_bytes(nseq, K) bytes, 16-byte
+ * aligned (the 16-bit mean plane [nseq, K], row stride K, written first); table: device fp32 [nseq, ldt].  Two small launches on
+ * `stream`. */
 long long mer_seq_bias_scratch_bytes(int nseq, int K);
 int mer_seq_bias(const void* a, int dtype, long long lda, int a_rows_per_batch, long long a_batch_stride, int M, int K,
                  int seg_rows, const int* valid_rows, const void* w_lo, long long ldw, const float* bias, int N, int n_first,

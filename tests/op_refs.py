@@ -1,7 +1,7 @@
 """Plain torch fp64 references of the op-level kernels (include/mer_hip.h), one function per op.
 
 Nothing here touches the GPU or imports the library: these are the yardsticks of tests/test_attention_matrix_gpu.py,
-tests/test_gemm_matrix_gpu.py and tests/test_rowops_gpu.py, and tests/test_op_refs_cpu.py pins them against torch's own operators.  Layouts are the ABI's:
+tests/test_gemm_matrix_gpu.py, tests/test_rowops_gpu.py and tests/test_seq_bias_gpu.py, and tests/test_op_refs_cpu.py pins them against torch's own operators.  Layouts are the ABI's:
 qkv is [B*T, 3*H*64] with the q | k | v column blocks, head h at columns 64 h .. 64 h + 63 of its block.
 """
 import torch
@@ -807,3 +807,166 @@ def group_diff(a, b):
             w["grad"] = max(w["grad"], max_rel(ra["grad0"], rb["grad0"]))
         w["param"] = max(w["param"], *(max_rel(ra[k], rb[k]) for k in ("flat", "m", "v")))
     return w
+
+
+# --------------------------------------------------------------------------------------------------------------- mer_seq_bias
+# (csrc/norm.hip: tests/test_seq_bias_gpu.py).  Restated from the words of include/mer_hip.h, not from the kernels.
+SEQ_FIX = 16384.0          # the 2^-14 grid a sample is rounded to
+SEQ_CLAMP = 131000.0       # ... after this clamp
+SEQ_MAX_SAMPLES = 32
+
+
+def seq_sample_stride(T):
+    """The largest power of two s with 16 s <= T (1 for T < 16)."""
+    return 1 << max((T // 16).bit_length() - 1, 0)
+
+
+def seq_sample_rows(T, valid, rows_left, mutate=None):
+    """The sampled rows of one sequence of T rows, relative to its first row: h, h + s, ... below min(valid, T, rows_left), s =
+    seq_sample_stride(T), h = s / 2; rows_left = what the plane still holds from the sequence's first row on.
+    mutate (the CPU sensitivity tests): "offset0", "stride2" (stride 2 s, offset kept), "drop_last", "no_valid"."""
+    s = seq_sample_stride(T)
+    h = 0 if mutate == "offset0" else s // 2
+    lim = min(T, rows_left) if mutate == "no_valid" else min(valid, T, rows_left)
+    rows = list(range(h, lim, 2 * s if mutate == "stride2" else s))
+    return rows[:-1] if mutate == "drop_last" else rows
+
+
+def round16_direct(x, dtype):
+    """fp64 -> the 16-bit format in ONE round-to-nearest-even step, returned as fp64 (torch's own fp64 -> 16-bit cast goes through
+    fp32).  No overflow handling: |x| stays below the format's largest value."""
+    p, emin = (11, -13) if T16[dtype] == torch.float16 else (8, -125)        # x = m 2^e, m in [0.5, 1): one ulp is 2^(e - p)
+    x = x.double()
+    _, e = torch.frexp(x)
+    q = torch.pow(torch.tensor(2.0, dtype=torch.float64), (e.clamp_min(emin) - p).double())
+    return torch.round(x / q) * q
+
+
+def seq_mean16_ref(a, seg_rows, valid=None, mutate=None):
+    """The 16-bit mean plane [ceil(M / seg_rows), K] of a 16-bit plane a [M, K], as an integer model — bit for bit what the header
+    promises: per sampled element rint(clamp(x, +-131000) 2^14) as int64 (ties to even; NaN counts as -131000), the samples summed,
+    float64(sum) * (1.0 / (total * 16384.0)), rounded to fp32 and then to the plane's dtype, both to nearest even.  A sequence with
+    no sample gives 0.  mutate: those of seq_sample_rows, and "no_f32" (fp64 -> 16 bits in one rounding)."""
+    M, K = a.shape
+    nseq = -(-M // seg_rows)
+    out = torch.zeros((nseq, K), dtype=a.dtype)
+    for s in range(nseq):
+        v = seg_rows if valid is None else int(valid[s])
+        rows = seq_sample_rows(seg_rows, v, M - s * seg_rows, mutate)
+        if not rows:
+            continue
+        x = a[[s * seg_rows + r for r in rows]].double()
+        x = torch.where(x.isnan(), torch.full_like(x, -SEQ_CLAMP), x.clamp(-SEQ_CLAMP, SEQ_CLAMP))
+        total = torch.round(x * SEQ_FIX).to(torch.int64).sum(0)
+        mean = total.double() * (1.0 / (len(rows) * SEQ_FIX))
+        out[s] = round16_direct(mean, a.dtype).to(a.dtype) if mutate == "no_f32" else mean.float().to(a.dtype)
+    return out
+
+
+def seq_sample_mean64(a, seg_rows, valid=None):
+    """The plain statement: the fp64 mean of the sampled rows themselves (finite inputs), 0 without a sample."""
+    M, K = a.shape
+    nseq = -(-M // seg_rows)
+    out = torch.zeros((nseq, K), dtype=torch.float64)
+    for s in range(nseq):
+        rows = seq_sample_rows(seg_rows, seg_rows if valid is None else int(valid[s]), M - s * seg_rows)
+        if rows:
+            out[s] = a[[s * seg_rows + r for r in rows]].double().mean(0)
+    return out
+
+
+def seq_mean16_plain_bound(mean64, dtype):
+    """|mean16 - fp64 mean of the samples| <= 2^-15 + one rounding to the dtype: every sample moves by at most half a grid step
+    (2^-15) when it is put on the 2^-14 grid, so does their mean; the two final roundings (fp32, then the dtype) cost u |y| of the
+    rounded value y, |y| <= |mean| + 2^-15, plus fp32's 2^-24 relative, and half the format's smallest subnormal step where y is
+    subnormal (f16: 2^-25)."""
+    m = mean64.abs() + 2.0 ** -15
+    return 2.0 ** -15 + (U16[dtype] + 2.0 ** -24 + 2.0 ** -52) * m + 2.0 ** -25
+
+
+def seq_ksplit(K):
+    """How the table product splits K over its 16 waves: (per, [(k_lo, k_hi)] * 16) in k-steps of 32 — used by the k-slice
+    mutation and the fp32 model only; the reference itself is a plain fp64 product."""
+    ksteps = -(-K // 32)
+    per = -(-ksteps // 16)
+    return per, [(min(w * per * 32, K), min((w + 1) * per * 32, K)) for w in range(16)]
+
+
+def seq_bias_table_ref(mean16, w_lo, bias=None, n_first=0, mutate=None):
+    """fp64 table[s, n] = mean16[s] . w_lo[n] + bias[n]; columns below n_first are exactly bias (0 without one).
+    mutate: "drop_kslice" (the second 32-wide k-step of wave 1 — or the last k-step, where K is too short — is left out),
+    "n_first_block" (the plain range ends one 16-column block later), "n_clamp_low" (the last column reads the row before it),
+    "no_n_clamp" (column n of a partial block reads row n of the w_lo BUFFER unclamped: w_lo must then hold ceil16(N) rows, and
+    only the first N columns are written — see tests/test_op_refs_cpu.py for what that does and does not move)."""
+    m, w = mean16.double(), w_lo.double()
+    K = m.shape[1]
+    N = w.shape[0]
+    if mutate == "no_n_clamp":
+        N = bias.shape[0] if bias is not None else N
+        assert w.shape[0] >= -(-N // 16) * 16
+        w = w[:-(-N // 16) * 16]
+    if mutate == "drop_kslice":
+        per, parts = seq_ksplit(K)
+        k0 = parts[1][0] + 32 if parts[1][0] + 32 < parts[1][1] else (K - 1) // 32 * 32
+        m = m.clone()
+        m[:, k0:k0 + 32] = 0
+    if mutate == "n_clamp_low":
+        w = torch.cat([w[:-1], w[-2:-1]]) if N > 1 else w
+    t = (m @ w.T)[:, :N]
+    t[:, :min(n_first + (16 if mutate == "n_first_block" else 0), N)] = 0
+    return t if bias is None else t + bias.double()
+
+
+def seq_bias_bound(mean16, w_lo, bias=None, n_first=0):
+    """Elementwise bound on |table - seq_bias_table_ref|: (K + 6) u S, u = 2^-24, S = |mean16| . |w_lo|^T + |bias|; 0 in the columns
+    below n_first (they are the bias itself).  Counted as gemm32_bound counts: the product of two 16-bit values (11 or 8
+    significand bits each) is exact in fp32, so only additions round; an output element is the root of a summation tree whose
+    leaves are the K products: whatever order the MFMA and the k-loop take them in, no leaf lies under more than K additions
+    inside its wave, 4 more in the fixed tree over the 16 k-split waves and 1 for the bias, each addition rounding its partial sum
+    (<= the magnitude sum of what is below it) by at most u: (K + 5) u S to first order.  The sixth u covers the second-order terms
+    of (1 + u)^(K + 5) for every K below 2^20.  Nothing here looks at the kernel's output."""
+    m, w = mean16.double().abs(), w_lo.double().abs()
+    S = m @ w.T
+    if bias is not None:
+        S = S + bias.double().abs()
+    b = (m.shape[1] + 6) * U32 * S
+    b[:, :min(n_first, b.shape[1])] = 0
+    return b
+
+
+def seq_bias_model32(mean16, w_lo, bias=None, n_first=0):
+    """One admissible fp32 evaluation of the table: per wave of seq_ksplit a running fp32 sum over its k-steps (each k-step's 32
+    products summed in fp32 by torch), the 16 partial sums through a pairwise tree, one bias add.  The CPU tests hold it to
+    seq_bias_bound: the bound is not tighter than honest fp32 arithmetic."""
+    m, w = mean16.float(), w_lo.float()
+    K = m.shape[1]
+    parts = []
+    for lo, hi in seq_ksplit(K)[1]:
+        acc = torch.zeros((m.shape[0], w.shape[0]), dtype=torch.float32)
+        for k in range(lo, hi, 32):
+            acc = acc + m[:, k:min(k + 32, hi)] @ w[:, k:min(k + 32, hi)].T
+        parts.append(acc)
+    d = 1
+    while d < 16:
+        for i in range(0, 16, 2 * d):
+            parts[i] = parts[i] + parts[i + d]
+        d *= 2
+    t = parts[0]
+    t[:, :min(n_first, t.shape[1])] = 0
+    return t if bias is None else t + bias.float()
+
+
+def seq_grid_values(shape, seed, dtype):
+    """Inputs on which the 2^-14 grid matters: magnitudes log-uniform over 2^-20 .. 8 with random signs, rounded to the dtype, every
+    third element an exact tie (n + 0.5) 2^-14 with n in 0 .. 63 (representable in both formats), every 29th an exact zero."""
+    g = torch.Generator().manual_seed(seed)
+    n = 1
+    for d in shape:
+        n *= d
+    x = 2.0 ** (torch.rand(n, generator=g, dtype=torch.float64) * 23.0 - 20.0)
+    x = x * (torch.randint(0, 2, (n,), generator=g) * 2 - 1)
+    tie = (torch.randint(0, 64, (n,), generator=g).double() + 0.5) / SEQ_FIX * (torch.randint(0, 2, (n,), generator=g) * 2 - 1)
+    idx = torch.arange(n)
+    x = torch.where(idx % 3 == 1, tie, x)
+    x = torch.where(idx % 29 == 5, torch.zeros_like(x), x)
+    return x.float().to(T16[dtype]).view(shape)

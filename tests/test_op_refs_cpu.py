@@ -423,3 +423,128 @@ def test_small_attention_bound_holds_for_fp32_and_is_tight_enough_to_bite():
     assert R.worst_ratio(out32, ref, bound) <= 1.0
     assert bound.max() <= 1e-3 * ref.abs().max()
     assert R.worst_ratio(R.small_attention_ref(q, k, v.roll(1, 0), B, Tq, Tk, H, 0.125), ref, bound) >= 100.0
+
+
+# --------------------------------------------------------------------------------------------------------------- mer_seq_bias
+def _brute_rows(T, valid, rows_left):
+    s = max(p for p in (2 ** i for i in range(13)) if p == 1 or 16 * p <= T)
+    return [r for r in range(T) if r % s == s // 2 and r < valid and r < rows_left]
+
+
+def test_seq_sample_rows_against_enumeration():
+    """Every T <= 2100, at valid / rows_left on both sides of every sample boundary; no T up to 5000 yields more than 32 samples, and
+    32 is first reached at T = 127."""
+    for T in range(1, 2101):
+        s = R.seq_sample_stride(T)
+        h = s // 2
+        assert s & (s - 1) == 0 and (s == 1 or 16 * s <= T) and 32 * s > T
+        for valid in {0, h, h + 1, h + s, h + s + 1, T - 1, T, T + 5}:
+            assert R.seq_sample_rows(T, valid, T) == _brute_rows(T, valid, T), (T, valid)
+        for left in {1, h, h + 1, T - 1} - {0}:
+            assert R.seq_sample_rows(T, T, left) == _brute_rows(T, T, left), (T, left)
+            assert R.seq_sample_rows(T, h + s + 1, left) == _brute_rows(T, h + s + 1, left), (T, left)
+    counts = [len(R.seq_sample_rows(T, T, T)) for T in range(1, 5001)]
+    assert max(counts) == R.SEQ_MAX_SAMPLES == 32 and counts.index(32) + 1 == 127
+    assert all(c >= min(T, 16) for T, c in enumerate(counts, 1))               # "leaves at least 16 samples" (all rows below T = 16)
+
+
+@pytest.mark.parametrize("dtype", ["f16", "bf16"])
+def test_round16_direct_is_the_formats_rounding(dtype):
+    """On fp32 inputs (no double rounding possible) the hand-written one-step rounding equals torch's cast, subnormals and ties
+    included."""
+    x = torch.cat([R.seq_grid_values((4096,), 3, "f16").float() * 1.0009765, R.rand((4096,), 4, 100.0),
+                   torch.tensor([1.0 + 2.0 ** -11, 1.0 + 3 * 2.0 ** -11, 2.0 ** -25, 3 * 2.0 ** -25, 2.0 ** -24, 0.0, -2.0 ** -14, 1.0 + 2.0 ** -8, 1.0 + 3 * 2.0 ** -8])])
+    assert torch.equal(R.round16_direct(x, dtype), x.to(R.T16[dtype]).double())
+
+
+def _mean_case(dtype, T=70, nseq=3, K=24):
+    a = R.seq_grid_values((T * nseq - 9, K), 11, dtype)
+    valid = torch.tensor([T, T - 13, T])[:nseq]
+    return a, T, valid
+
+
+@pytest.mark.parametrize("dtype", ["f16", "bf16"])
+def test_seq_mean16_ref_plain_statement_and_controls(dtype):
+    """The integer model keeps the plain statement (|mean16 - fp64 sample mean| <= 2^-15 + the roundings), and every mutation of the
+    sample moves at least one bit of the plane."""
+    a, T, valid = _mean_case(dtype)
+    good = R.seq_mean16_ref(a, T, valid)
+    m64 = R.seq_sample_mean64(a, T, valid)
+    assert R.worst_ratio(good, m64, R.seq_mean16_plain_bound(m64, dtype)) <= 1.0
+    assert (good.double() != m64).any(), "the grid must matter on these inputs"
+    # an independent restatement in exact rational arithmetic
+    from fractions import Fraction
+    s, h = R.seq_sample_stride(T), R.seq_sample_stride(T) // 2
+    rows = list(range(T + h, T + min(int(valid[1]), T), s))
+    for k in (0, 7, 23):
+        tot = sum(round(Fraction(float(a[r, k])) * 16384) for r in rows)          # round(): ties to even, exact
+        want = torch.tensor(float(tot) * (1.0 / (len(rows) * 16384.0)), dtype=torch.float64).float().to(a.dtype)
+        assert good[1, k].item() == want.item()
+    for mut in ("offset0", "stride2", "drop_last", "no_valid"):
+        bad = R.seq_mean16_ref(a, T, valid, mutate=mut)
+        assert not torch.equal(bad.view(torch.int16), good.view(torch.int16)), mut
+    # no sample: valid = h, and a last sequence with h rows left
+    z = R.seq_mean16_ref(a[:2 * T + h], T, torch.tensor([h, T, T]))
+    assert not z[0].any() and not z[2].any() and z[1].any()
+
+
+@pytest.mark.parametrize("dtype,big,odd", [("f16", 1024.0, 2056.0), ("bf16", 128.0, 264.0)])
+def test_seq_mean16_ref_rounds_through_fp32(dtype, big, odd):
+    """16 samples whose mean is half an ulp of the 16-bit format above `big`, plus 2^-18: fp32 drops the 2^-18, the tie then goes
+    to even; one rounding from fp64 goes up.  The model must give the former."""
+    col = torch.tensor([big] * 14 + [odd, 2.0 ** -14]).to(R.T16[dtype])
+    assert col.double().sum().item() == 16 * (big + 0.5) + 2.0 ** -14
+    a = col[:, None].repeat(1, 8)
+    good, direct = R.seq_mean16_ref(a, 16), R.seq_mean16_ref(a, 16, mutate="no_f32")
+    assert good[0, 0].item() == big and direct[0, 0].item() == big + 1.0           # one ulp of either format at `big` is 1
+
+
+def test_seq_mean16_ref_clamp_and_nonfinite():
+    """bf16 samples of 2^17 and 2^20 count as 131000; +inf as 131000, -inf and NaN as -131000."""
+    a = torch.zeros((16, 8), dtype=torch.bfloat16)
+    a[:, 0] = 2.0 ** 17
+    a[::2, 1] = 2.0 ** 20
+    a[3, 2] = float("inf")
+    a[3, 3] = float("nan")
+    a[3, 4] = float("-inf")
+    m = R.seq_mean16_ref(a, 16).double()
+    want = torch.tensor([131000.0, 65500.0, 131000.0 / 16, -131000.0 / 16, -131000.0 / 16, 0, 0, 0]).bfloat16().double()
+    assert torch.equal(m[0], want)
+
+
+def _table_case(K, N, nseq, dtype, bias=True):
+    mean16 = (R.rand((nseq, K), 21) * 0.7 + 0.3).to(R.T16[dtype])
+    w_lo = R.rand((-(-N // 16) * 16, K), 22).to(R.T16[dtype])             # order 1, with the rows a partial block would overread
+    return mean16, w_lo, (R.rand((N,), 23) if bias else None)
+
+
+@pytest.mark.parametrize("dtype", ["f16", "bf16"])
+@pytest.mark.parametrize("K,N,n_first", [(8, 17, 0), (40, 40, 32), (544, 16, 0), (2080, 40, 16)])
+def test_seq_bias_bound_holds_fp32_and_sees_the_mutations(dtype, K, N, n_first):
+    """An honest fp32 evaluation in the kernel's shape stays inside seq_bias_bound; a dropped k-slice, a clamp one column low and an
+    n_first one block off are each at least 100 bounds out."""
+    mean16, wbuf, bias = _table_case(K, N, 5, dtype)
+    w_lo = wbuf[:N]
+    ref = R.seq_bias_table_ref(mean16, w_lo, bias, n_first)
+    bound = R.seq_bias_bound(mean16, w_lo, bias, n_first)
+    assert torch.equal(ref[:, :n_first], bias.double()[None, :n_first].expand(5, -1))
+    assert R.worst_ratio(R.seq_bias_model32(mean16, w_lo, bias, n_first), ref, bound) <= 1.0
+    for mut in ("drop_kslice", "n_clamp_low", "n_first_block"):
+        bad = R.seq_bias_table_ref(mean16, w_lo, bias, n_first, mutate=mut)
+        assert R.worst_ratio(bad, ref, bound.clamp_min(1e-30)) >= 100.0, mut
+
+
+def test_a_missing_n_clamp_is_a_read_not_a_value():
+    """Column n of the table depends on row n of w_lo alone, so lanes 16 .. ceil16(N) - 1 of a partial column block, whose columns are
+    never written, cannot move a written value whatever they read: without the clamp they read rows N .. of the buffer (NaN here),
+    and the N written columns are the reference's, bit for bit.  What the clamp is for is the READ — the GPU test surrounds w_lo with
+    NaN rows it does not own — and the value-moving neighbour of that defect is the clamp taken one row low ("n_clamp_low")."""
+    mean16, wbuf, bias = _table_case(40, 17, 5, "f16")
+    wbuf = wbuf.clone()
+    wbuf[17:] = float("nan")
+    ref = R.seq_bias_table_ref(mean16, wbuf[:17], bias)
+    free = R.seq_bias_table_ref(mean16, wbuf, bias, mutate="no_n_clamp")
+    assert free.shape == ref.shape and torch.equal(free, ref)
+    low = R.seq_bias_table_ref(mean16, wbuf[:17], bias, mutate="n_clamp_low")
+    assert torch.equal(low[:, :16], ref[:, :16])
+    assert R.worst_ratio(low, ref, R.seq_bias_bound(mean16, wbuf[:17], bias)) >= 100.0

@@ -669,6 +669,30 @@ int mer_image_resize_crop_u8(const unsigned char* frames, int N, int H, int W, i
 /* SwiGLU gate: out[m, j] = silu(y[m, j]) * y[m, F + j] for y fp32 [M, 2F] (row stride ldy) -> 16-bit planes [M, F]. */
 int mer_swiglu(const float* y, long long ldy, int M, int F, void* out_hi, void* out_lo, int dtype, mer_stream_t stream);
 
+/* ---- LLaMA-family decoder-only text models (mertools_amd/llama.py; HF:llama/modeling_llama.py) ----
+ * y = (x * rsqrt(mean(x^2) + eps)) * gamma over the last dim D, all in fp32 and in this order (LlamaRMSNorm); gamma == NULL means ones.
+ * x: fp32 rows with stride ldx.  Optional outputs, at least one: fp32 (out32, ld32) and 16-bit planes (out16_hi = the fp32 result
+ * rounded once, out16_lo = the rounded remainder, may be NULL; both with stride ld16).  D % 4 == 0, 4 <= D <= 8192; ldx, ld32, ld16
+ * multiples of 4 and >= D; x, gamma, out32 16-byte aligned.  One kernel for every M: row r's bits depend on row r alone.
+ * No allocation, no synchronisation, no atomics; bad arguments return a negative status before any launch. */
+int mer_rmsnorm(const float* x, long long ldx, const float* gamma, float eps, int M, int D, float* out32, long long ld32,
+                void* out16_hi, void* out16_lo, long long ld16, int dtype, mer_stream_t stream);
+
+/* Causal softmax attention with the rotary position embedding applied to q and k as they are loaded (LlamaAttention, eager, fp32).
+ * q, k, v: device fp32 [B*T, ld] (the fp32 output of the fused QKV GEMM), head h at column h * head_dim of each pointer; ld % 4 == 0,
+ * 16-byte aligned.  cos / sin: fp32 [T, head_dim / 2] tables built by the caller (row t = position t of every sentence; the device
+ * evaluates no trigonometric function).  With h = head_dim / 2 (HF's rotate_half):
+ *   d <  h: q'[d] = q[d] cos[t, d]     - q[d + h] sin[t, d]
+ *   d >= h: q'[d] = q[d] cos[t, d - h] + q[d - h] sin[t, d - h]          (the same for k)
+ * out[b, t] = softmax_{k <= t}(q'[b, t] . k'[b, k] * scale) v[b, k]: scores, maximum-subtracted softmax, its sum and 1 / sum in fp32
+ * on plain FMAs.  out_hi / out_lo: 16-bit hi / lo planes of the context rows, row-major [B*T, ldo] (out_lo may be NULL) — what
+ * mer_attention_f32 writes.  head_dim 64 or 128, 1 <= T <= 2048, everything else is refused before any launch.  Row (b, t) depends on
+ * rows (b, 0..t) only: its bits change neither with B nor with T (right padding), whatever the later rows hold.
+ * No allocation, no synchronisation, no atomics. */
+int mer_rope_attention(const float* q, const float* k, const float* v, long long ld, const float* cos, const float* sin,
+                       void* out_hi, void* out_lo, long long ldo, int B, int T, int H, int head_dim, float scale, int dtype,
+                       mer_stream_t stream);
+
 /* out[n, :] = scale * sum over t of x[n, t, :]   (x fp32 [N, T, D]; token sum / mean of a hidden state). */
 int mer_token_reduce(const float* x, int N, int T, int D, float scale, float* out, mer_stream_t stream);
 

@@ -370,6 +370,52 @@ def swiglu(y, F, *, dtype="f16", lo=False):
     return oh, ol
 
 
+def rmsnorm(x, gamma, eps, *, out32=True, out16=False, out16_lo=False, dtype="f16", M=None, D=None, ldx=None, out=None):
+    """LlamaRMSNorm, (x * rsqrt(mean(x^2) + eps)) * gamma (gamma None: ones), over fp32 rows (mer_rmsnorm) -> (o32, hi, lo) like
+    layernorm(); out: optional caller-owned (o32, hi, lo) [M, D] views whose row strides become ld32 / ld16."""
+    D = D if D is not None else x.shape[-1]
+    M = M if M is not None else x.numel() // D
+    ldx = ldx if ldx is not None else D
+    dev = x.device
+    if out is not None:
+        o32, oh, ol = out
+        assert ol is None or (oh is not None and ol.stride(0) == oh.stride(0))
+    else:
+        o32 = torch.empty((M, D), dtype=torch.float32, device=dev) if out32 else None
+        oh = torch.empty((M, D), dtype=torch16(dtype), device=dev) if out16 else None
+        ol = torch.empty((M, D), dtype=torch16(dtype), device=dev) if (out16 and out16_lo) else None
+    _lib.check(_lib.lib().mer_rmsnorm(_p(x), ldx, _p(gamma), eps, M, D, _p(o32), _ld(o32, D), _p(oh), _p(ol), _ld(oh, D), dt_code(dtype), stream()),
+               "mer_rmsnorm")
+    return o32, oh, ol
+
+
+def rope_tables(T, head_dim, theta=10000.0, device=None):
+    """(cos, sin) fp32 [T, head_dim / 2] as HF's LlamaRotaryEmbedding builds them (default rope type): inv_freq and the angle
+    position * inv_freq in fp32 on the host, then cos / sin.  (HF's tables are this one concatenated with itself.)"""
+    inv_freq = 1.0 / (theta ** (torch.arange(0, head_dim, 2, dtype=torch.int64).to(torch.float32) / head_dim))
+    ang = torch.arange(T, dtype=torch.float32)[:, None] * inv_freq[None, :]
+    cos, sin = ang.cos().contiguous(), ang.sin().contiguous()
+    return (cos.to(device), sin.to(device)) if device is not None else (cos, sin)
+
+
+def rope_attention(qkv32, cos, sin, B, T, H, head_dim, scale, *, out_lo=True, dtype="f16", out=None):
+    """qkv32: fp32 [B*T, >= 3*H*head_dim] (q | k | v column blocks; a wider row stride is fine), cos / sin fp32 [>= T, head_dim / 2]
+    (rope_tables) -> causal rotary attention, ctx hi (+ lo) 16-bit planes [B*T, H*head_dim] (mer_rope_attention)."""
+    D = H * head_dim
+    assert qkv32.dtype == torch.float32 and qkv32.dim() == 2 and qkv32.shape[0] == B * T and qkv32.shape[1] >= 3 * D and qkv32.stride(1) == 1
+    assert cos.dtype == sin.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous()
+    assert cos.shape == sin.shape and cos.shape[0] >= T and cos.shape[1] == head_dim // 2
+    if out is not None:
+        oh, ol = out
+        assert ol is None or ol.stride(0) == oh.stride(0)
+    else:
+        oh = torch.empty((B * T, D), dtype=torch16(dtype), device=qkv32.device)
+        ol = torch.empty_like(oh) if out_lo else None
+    _lib.check(_lib.lib().mer_rope_attention(qkv32.data_ptr(), qkv32.data_ptr() + D * 4, qkv32.data_ptr() + 2 * D * 4, qkv32.stride(0), _p(cos), _p(sin),
+                                             _p(oh), _p(ol), oh.stride(0), B, T, H, head_dim, float(scale), dt_code(dtype), stream()), "mer_rope_attention")
+    return oh, ol
+
+
 def token_reduce(x, scale=1.0):
     """x fp32 [N, T, D] -> scale * x.sum(1), fp32 [N, D] (mer_token_reduce)."""
     assert x.dim() == 3 and x.dtype == torch.float32 and x.is_contiguous()

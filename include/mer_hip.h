@@ -693,6 +693,25 @@ int mer_rope_attention(const float* q, const float* k, const float* v, long long
                        void* out_hi, void* out_lo, long long ldo, int B, int T, int H, int head_dim, float scale, int dtype,
                        mer_stream_t stream);
 
+/* ---- BLOOM-family decoder-only text models (mertools_amd/bloom.py; HF:bloom/modeling_bloom.py) ----
+ * F.layer_norm over rows up to 8192 wide (mer_layernorm stops at 2048): mean, biased variance of the CENTRED values,
+ * y = (x - mean) * rsqrt(var + eps) * gamma + beta, all in fp32 (gamma == NULL means ones, beta == NULL zeros).  Arguments, outputs,
+ * alignment and refusals as mer_rmsnorm; one kernel for every M and every D: row r's bits depend on row r alone.
+ * No allocation, no synchronisation, no atomics; bad arguments return a negative status before any launch. */
+int mer_layernorm_row(const float* x, long long ldx, const float* gamma, const float* beta, float eps, int M, int D, float* out32,
+                      long long ld32, void* out16_hi, void* out16_lo, long long ld16, int dtype, mer_stream_t stream);
+
+/* Causal softmax attention with ALiBi (Press et al.; BloomAttention, Baichuan-13B): mer_rope_attention's contract without the
+ * rotation and with a per-head linear distance bias.  slopes: device fp32 [H], built by the caller.
+ *   out[b, t] = softmax_{j <= t}(q[b, t] . k[b, j] * scale + slopes[h] * (j - t)) v[b, j]
+ * The bias is the relative form: 0 on the diagonal and <= 0 before it, which softmax's shift invariance makes equal to HF's
+ * slopes[h] * j; j is the token index within the sentence.  slopes[h] == 0 gives plain causal attention.  q, k, v, out_hi / out_lo,
+ * ld / ldo, head_dim 64 or 128, 1 <= T <= 2048, alignment and refusals as mer_rope_attention (slopes: 4-byte aligned).  Row (b, t)
+ * depends on rows (b, 0..t) only: its bits change neither with B nor with T (right padding), whatever the later rows hold.
+ * No allocation, no synchronisation, no atomics. */
+int mer_alibi_attention(const float* q, const float* k, const float* v, long long ld, const float* slopes, void* out_hi, void* out_lo,
+                        long long ldo, int B, int T, int H, int head_dim, float scale, int dtype, mer_stream_t stream);
+
 /* out[n, :] = scale * sum over t of x[n, t, :]   (x fp32 [N, T, D]; token sum / mean of a hidden state). */
 int mer_token_reduce(const float* x, int N, int T, int D, float scale, float* out, mer_stream_t stream);
 

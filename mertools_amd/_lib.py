@@ -257,6 +257,9 @@ _PROTOS = {
     "mer_rmsnorm": (c_int, [c_void_p, c_ll, c_void_p, c_float, c_int, c_int, c_void_p, c_ll, c_void_p, c_void_p, c_ll, c_int, c_void_p]),
     "mer_rope_attention": (c_int, [c_void_p, c_void_p, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_int, c_int, c_int, c_int,
                                    c_float, c_int, c_void_p]),
+    "mer_layernorm_row": (c_int, [c_void_p, c_ll, c_void_p, c_void_p, c_float, c_int, c_int, c_void_p, c_ll, c_void_p, c_void_p, c_ll, c_int, c_void_p]),
+    "mer_alibi_attention": (c_int, [c_void_p, c_void_p, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_ll, c_int, c_int, c_int, c_int,
+                                    c_float, c_int, c_void_p]),
     "mer_token_reduce": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     "mer_videomae_create": (c_int, [C.POINTER(VideoMAEConfig), C.POINTER(VideoMAEWeights), C.POINTER(c_void_p)]),
     "mer_videomae_destroy": (None, [c_void_p]),

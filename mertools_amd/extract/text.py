@@ -1,6 +1,6 @@
 """Text feature extraction — mirror of MERBench/feature_extraction/text/extract_text_huggingface.py:90-252 for the
-encoder-only (BERT / RoBERTa family) models and the LLaMA-architecture decoder-only ones (mertools_amd/llama.py, picked by the
-checkpoint's model_type).  Special-token probing and .npy rules are the reference's; sentences are right-padded into batches with
+encoder-only (BERT / RoBERTa family) models and the LLaMA- and BLOOM-architecture decoder-only ones (mertools_amd/llama.py,
+mertools_amd/bloom.py, picked by the checkpoint's model_type).  Special-token probing and .npy rules are the reference's; sentences are right-padded into batches with
 per-row key-length masking on the HIP encoder (causal attention needs none)."""
 import os
 import time
@@ -89,9 +89,13 @@ def extract_embedding(model_name, trans_dir, save_dir, feature_level, gpu=-1, pu
             model_dir = os.path.join(config.PATH_TO_PRETRAINED_MODELS, f'transformers/{model_name}')
         torch.cuda.set_device(max(gpu, 0))   # reference: torch.cuda.set_device(gpu) (extract_text_huggingface.py:192-193)
         from transformers import AutoConfig
-        if AutoConfig.from_pretrained(model_dir).model_type == 'llama':   # decoder-only LLaMA family (the reference's .half() at :193 is
+        model_type = AutoConfig.from_pretrained(model_dir).model_type
+        if model_type == 'llama':                                          # decoder-only LLaMA family (the reference's .half() at :193 is
             from ..llama import HipLlamaModel                              # not mirrored: the parity target is the fp32 module)
             model = HipLlamaModel.from_hf(AutoModel.from_pretrained(model_dir), device=f'cuda:{max(gpu, 0)}')
+        elif model_type == 'bloom':                                        # decoder-only BLOOM family, the same rule
+            from ..bloom import HipBloomModel
+            model = HipBloomModel.from_hf(AutoModel.from_pretrained(model_dir), device=f'cuda:{max(gpu, 0)}')
         else:
             model = HipBertModel.from_hf(AutoModel.from_pretrained(model_dir), device=f'cuda:{max(gpu, 0)}')
         tokenizer = AutoTokenizer.from_pretrained(model_dir, use_fast=False)

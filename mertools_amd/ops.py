@@ -4,6 +4,8 @@ torch is used for device memory and the current stream only; every computation b
 HIP kernel of libmer_hip.so.  These wrappers exist for the parity tests and for composing the
 encoders; they validate devices/dtypes and otherwise pass raw pointers through.
 """
+import math
+
 import torch
 
 from . import _lib
@@ -413,6 +415,56 @@ def rope_attention(qkv32, cos, sin, B, T, H, head_dim, scale, *, out_lo=True, dt
         ol = torch.empty_like(oh) if out_lo else None
     _lib.check(_lib.lib().mer_rope_attention(qkv32.data_ptr(), qkv32.data_ptr() + D * 4, qkv32.data_ptr() + 2 * D * 4, qkv32.stride(0), _p(cos), _p(sin),
                                              _p(oh), _p(ol), oh.stride(0), B, T, H, head_dim, float(scale), dt_code(dtype), stream()), "mer_rope_attention")
+    return oh, ol
+
+
+def layernorm_row(x, gamma, beta, eps, *, out32=True, out16=False, out16_lo=False, dtype="f16", M=None, D=None, ldx=None, out=None):
+    """F.layer_norm over fp32 rows up to 8192 wide, centred variance (mer_layernorm_row; gamma / beta None: ones / zeros) -> (o32, hi, lo)
+    like rmsnorm(); out: optional caller-owned (o32, hi, lo) [M, D] views whose row strides become ld32 / ld16."""
+    D = D if D is not None else x.shape[-1]
+    M = M if M is not None else x.numel() // D
+    ldx = ldx if ldx is not None else D
+    dev = x.device
+    if out is not None:
+        o32, oh, ol = out
+        assert ol is None or (oh is not None and ol.stride(0) == oh.stride(0))
+    else:
+        o32 = torch.empty((M, D), dtype=torch.float32, device=dev) if out32 else None
+        oh = torch.empty((M, D), dtype=torch16(dtype), device=dev) if out16 else None
+        ol = torch.empty((M, D), dtype=torch16(dtype), device=dev) if (out16 and out16_lo) else None
+    _lib.check(_lib.lib().mer_layernorm_row(_p(x), ldx, _p(gamma), _p(beta), eps, M, D, _p(o32), _ld(o32, D), _p(oh), _p(ol), _ld(oh, D), dt_code(dtype),
+                                            stream()), "mer_layernorm_row")
+    return o32, oh, ol
+
+
+def alibi_slopes(H, device=None):
+    """fp32 [H] ALiBi slopes, bit for bit those of HF's build_alibi_tensor (bloom/modeling_bloom.py): fp32 torch.pow of the base
+    2^-(2^-(log2(n) - 3)) to the integer powers 1..n for the largest power of two n <= H, then the odd powers of the base of 2n for the
+    remaining heads."""
+    n = 2 ** math.floor(math.log2(H))
+    base = torch.full((), 2 ** (-(2 ** -(math.log2(n) - 3))), dtype=torch.float32)
+    slopes = torch.pow(base, torch.arange(1, 1 + n, dtype=torch.int32))
+    if n != H:
+        extra_base = torch.full((), 2 ** (-(2 ** -(math.log2(2 * n) - 3))), dtype=torch.float32)
+        extra = torch.arange(1, 1 + 2 * min(n, H - n), 2, dtype=torch.int32)
+        slopes = torch.cat([slopes, torch.pow(extra_base, extra)], dim=0)
+    return slopes.to(device) if device is not None else slopes
+
+
+def alibi_attention(qkv32, slopes, B, T, H, head_dim, scale, *, out_lo=True, dtype="f16", out=None):
+    """qkv32: fp32 [B*T, >= 3*H*head_dim] (q | k | v column blocks; a wider row stride is fine), slopes fp32 [H] (alibi_slopes) -> causal
+    attention with the bias slopes[h] * (j - t), ctx hi (+ lo) 16-bit planes [B*T, H*head_dim] (mer_alibi_attention)."""
+    D = H * head_dim
+    assert qkv32.dtype == torch.float32 and qkv32.dim() == 2 and qkv32.shape[0] == B * T and qkv32.shape[1] >= 3 * D and qkv32.stride(1) == 1
+    assert slopes.dtype == torch.float32 and slopes.is_contiguous() and slopes.shape == (H,) and slopes.device == qkv32.device
+    if out is not None:
+        oh, ol = out
+        assert ol is None or ol.stride(0) == oh.stride(0)
+    else:
+        oh = torch.empty((B * T, D), dtype=torch16(dtype), device=qkv32.device)
+        ol = torch.empty_like(oh) if out_lo else None
+    _lib.check(_lib.lib().mer_alibi_attention(qkv32.data_ptr(), qkv32.data_ptr() + D * 4, qkv32.data_ptr() + 2 * D * 4, qkv32.stride(0), _p(slopes),
+                                              _p(oh), _p(ol), oh.stride(0), B, T, H, head_dim, float(scale), dt_code(dtype), stream()), "mer_alibi_attention")
     return oh, ol
 
 
